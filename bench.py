@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the proposed-loss training step (BASELINE.json metric: training images/sec).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,9 +13,10 @@ default ConvolutionalModel (hidden 32, 5 scales, 645,063,043 parameters), per-GP
 256 / 8), synthetic inputs resident in HBM, random-init weights (torch.manual_seed(0)).
 
 The LAST stdout line of rank 0 is the contract's ONE JSON line -- the headline only, kept under 8 kB (`compact_line`;
-tests/test_bench_line.py) so that the driver parses it. Every secondary series is printed in full on an EARLIER line
-(`{"series": "<name>", ...}`) and the whole uncompacted object goes to gpurun_out/bench_full.json (or $SEI_BENCH_FULL).
-The headline carries these extra objects:
+tests/test_bench_line.py) so that the driver parses it. A plain run sets up, warms up, times the K steps and prints
+that line (`roofline` / `roofline_hbm` null). --full adds everything else: every secondary series is printed in full on
+an EARLIER line (`{"series": "<name>", ...}`), the whole uncompacted object goes to a side file (bench_full.json, see
+`emit`, or $SEI_BENCH_FULL), and the headline carries these extra objects:
   roofline     -- the dominant kernel family (the bf16 MFMA GEMMs: all 1x1 convolutions and their gradients),
                   every launch of one step re-issued between HIP events on the launch stream.
   roofline_hbm -- the streaming kernel families of the same step (Adam, depthwise 7x7, LayerNorm, ideal resamplers,
@@ -419,7 +420,7 @@ def dist1_child(opt, grad_comm=None, timeout=420):
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0",
                SEI_BENCH_FULL=os.path.join(ROOT, "gpurun_out", f"bench_full_dist1_{grad_comm}.json"))
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "10", "--warmup", "3", "--batch",
-           str(opt.batch), "--no-secondary", "--no-cpu-baseline", "--grad-comm", grad_comm, "--grad-comm-mode",
+           str(opt.batch), "--full", "--no-secondary", "--no-cpu-baseline", "--grad-comm", grad_comm, "--grad-comm-mode",
            opt.grad_comm_mode]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
@@ -823,7 +824,39 @@ def rooflines(leg, dtype, ms_step, pmc_traffic=False):
     return roofline, roofline_hbm
 
 
-def main():
+DUMP_ELEMENTS = 1 << 22      # per sampled array (16 MB of float32): three of them stay under 64 MB whatever the architecture
+
+
+def dump_outputs(leg, loss, out_dir, write):
+    """`--dump-outputs`: what a caller of the timed step holds after its last step -- the loss, the updated float32 weights
+    and both Adam moments -- as float32 .npy files, so that two builds can be compared output for output. The bucket is
+    2.6 GB: every parameter tensor contributes the same number of elements at positions drawn from a fixed seed (all of
+    it when smaller), so that each layer is covered. Collective under a sharded optimizer step (every rank calls it).
+    Compare with a norm-wise tolerance: float atomics in the GEMM and convolution kernels make the step not bitwise
+    repeatable -- two runs of one build (5 + 20 steps) differed by relative L2 5e-6 in the loss, 2e-5 in the weights and
+    3e-4 in the moments."""
+    import numpy as np
+    leg.optimizer.consolidate()                              # other ranks' shares of the weights and moments, if sharded
+    if not write:
+        return
+    slices = list(leg.optimizer._slices())
+    per_tensor = max(1, DUMP_ELEMENTS // len(slices))
+    g = torch.Generator().manual_seed(0)
+    picks = []
+    for p, off in slices:
+        n = p.numel()
+        pick = torch.arange(n) if n <= per_tensor else torch.randint(0, n, (per_tensor,), generator=g).sort().values
+        picks.append(pick + off)
+    index = torch.cat(picks).to(leg.backbone.flat_params.device)
+    st = leg.optimizer.state[leg.backbone.flat_params]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float32))
+    for name, buf in (("weights", leg.backbone.flat_params), ("adam_exp_avg", st["exp_avg"]),
+                      ("adam_exp_avg_sq", st["exp_avg_sq"])):
+        np.save(os.path.join(out_dir, f"{name}_sample.npy"), buf[index].float().cpu().numpy())
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -831,13 +864,19 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--hidden", type=int, default=32)
     ap.add_argument("--scales", type=int, default=5)
-    ap.add_argument("--cpu-baseline", action=argparse.BooleanOptionalAction, default=True)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the roofline legs, the secondary series and the CPU baseline "
+                         "(each can still be switched off by its own --no-* option); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): the loss, "
+                         "and a fixed sample of the updated weights and of both Adam moments")
+    ap.add_argument("--cpu-baseline", action=argparse.BooleanOptionalAction, default=None, help="default: --full")
     ap.add_argument("--cpu-batch", type=int, default=4, help="batch of the CPU baseline (BASELINE.md section 3: 4)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU steps after one warm-up step")
-    ap.add_argument("--profile-gemms", action=argparse.BooleanOptionalAction, default=True,
-                    help="the roofline legs (GEMM family + streaming families) after the timed region")
-    ap.add_argument("--secondary", action=argparse.BooleanOptionalAction, default=True,
-                    help="N=1: also time a short run in the reference's own arithmetic (float32 GEMMs)")
+    ap.add_argument("--profile-gemms", action=argparse.BooleanOptionalAction, default=None,
+                    help="the roofline legs (GEMM family + streaming families) after the timed region (default: --full)")
+    ap.add_argument("--secondary", action=argparse.BooleanOptionalAction, default=None,
+                    help="N=1: also time a short run in the reference's own arithmetic (float32 GEMMs) (default: --full)")
     ap.add_argument("--grad-comm", choices=["auto", "f32", "bf16"], default="auto",
                     help="dtype of the exchanged gradient bucket (auto = f32, as train.py's --grad_comm_dtype default; bf16 is the "
                          "opt-in compressed exchange of both)")
@@ -871,7 +910,17 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16", "bf16x3"], default="bf16",
                     help="arithmetic type of the 1x1-conv GEMMs (f32 = parity mode, bf16 = throughput mode, bf16x3 = split-bf16 "
                          "parity mode: three bf16 MFMA products per float32 product)")
-    opt = ap.parse_args()
+    opt = ap.parse_args(argv)
+    if opt.steps < 1 or opt.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    for key in ("cpu_baseline", "profile_gemms", "secondary"):
+        if getattr(opt, key) is None:
+            setattr(opt, key, opt.full)
+    return opt
+
+
+def main():
+    opt = parse_args()
 
     import parallel
     rank, local_rank, world = parallel.init_from_env()
@@ -897,6 +946,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     ms_step = 1e3 * elapsed / opt.steps
+    if opt.dump_outputs:
+        dump_outputs(leg, loss_value, opt.dump_outputs, rank == 0)
 
     roofline, roofline_hbm = (None, None)
     if opt.profile_gemms:
@@ -1007,7 +1058,10 @@ def main():
             out["cpu_baseline"] = cpu_baseline(opt.cpu_batch, opt.hidden, opt.scales, opt.cpu_steps)
             if secondary is not None and "swinir_sr2" in secondary:
                 out["cpu_baseline_swinir"] = cpu_baseline_swinir(opt.cpu_batch)
-        emit(out)
+        if opt.full:
+            emit(out)
+        else:
+            print(compact_line(out), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
 

@@ -114,12 +114,14 @@ def _fwd_vjp(fn, x, seed):
 def gen_noise2inverse():
     """G12: src/noise2inverse.py (numpy / torch only, imported by path).  Row slices + FFT inverse filter
     (ImageSlices, deblurring), the X:1 training pair of Noise2InverseTransform (numpy seed 3) and the summed
-    reconstruction of Noise2InverseModel around a fixed pointwise backbone."""
+    reconstruction of Noise2InverseModel around a fixed pointwise backbone.  In float64: the Gaussian's transfer
+    values fall to ~1e-9, below float32 resolution, so float32 slices are set by the FFT's own rounding and differ from
+    one CPU to the next; in float64 any FFT reproduces them to ~1e-7."""
     os.makedirs(OUT, exist_ok=True)
     n2i = _load_by_path("ref_noise2inverse", os.path.join(REF_SRC, "noise2inverse.py"))
     kernels = _load_by_path("ref_kernels", os.path.join(REF_SRC, "physics", "kernels.py"))
-    kernel = kernels.get_kernel("Gaussian_R2")[None, None].to(torch.float32)
-    y = _rand((2, 3, 16, 20), 31)
+    kernel = kernels.get_kernel("Gaussian_R2")[None, None].to(torch.float64)
+    y = _rand((2, 3, 16, 20), 31, torch.float64)
     arrs = {"y": _np(y), "kernel": _np(kernel)}
     slicer = n2i.ImageSlices(num_splits=4, task="deblurring", physics_filter=kernel, degradation_inverse_fn=None)
     for j, t in enumerate(slicer(y)):
