@@ -294,10 +294,16 @@ def call(name, *args):
         raise NativeLibraryError(f"{name} failed: {what}")
 
 
+def aligned(*tensors, to=16):
+    """True when every tensor given (None skipped) starts on a `to`-byte boundary. The vectorised kernels SEI_REQUIRE it of
+    their operands; a contiguous view at a storage offset (y[1:] of images with an odd number of floats) need not be."""
+    return all(t is None or t.data_ptr() % to == 0 for t in tensors)
+
+
 def scale_by(x, scalar):
     """x * scalar for a 0-dim device `scalar` (the incoming gradient of a loss value): one own launch where it applies."""
-    if x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() % 4 == 0 and isinstance(scalar, torch.Tensor) \
-            and scalar.is_cuda and scalar.dtype == torch.float32 and scalar.numel() == 1:
+    if x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() % 4 == 0 and aligned(x) \
+            and isinstance(scalar, torch.Tensor) and scalar.is_cuda and scalar.dtype == torch.float32 and scalar.numel() == 1:
         out = torch.empty_like(x)
         call("sei_scale_dev_f32", x.data_ptr(), scalar.data_ptr(), out.data_ptr(), x.numel())
         return out
@@ -307,7 +313,7 @@ def scale_by(x, scalar):
 def copy_into(dst, a, b=None):
     """dst <- a (b None) or the concatenation [a | b] along the leading dimension, as one own launch where it applies."""
     ok = all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() % 4 == 0)
-             for t in (dst, a, b))
+             for t in (dst, a, b)) and aligned(dst, a, b)
     if ok and dst.numel() == a.numel() + (0 if b is None else b.numel()):
         call("sei_concat2_f32", a.data_ptr(), a.numel(), ptr(b), 0 if b is None else b.numel(), dst.data_ptr())
         return dst

@@ -16,6 +16,7 @@ import torch
 from torch.nn import Module
 from torch.nn.functional import l1_loss
 
+import _native as N
 from crop import CropPair
 from physics._ops import axpy
 from transforms import CombinedTransform, Rotate, ScalingTransform, Shift
@@ -146,8 +147,7 @@ def _sum_terms(a, b):
 def _stacked_probe_input(y, b, tau):
     """[y, y + tau b] along the batch: the input of the fused 2B pass (src/losses/sure.py:24 beside the model call on y)."""
     if y.is_cuda and y.dtype == torch.float32 and b.dtype == torch.float32 and y.is_contiguous() and b.is_contiguous() \
-            and y.shape == b.shape and y.numel() % 4 == 0 and not (y.requires_grad or b.requires_grad):
-        import _native as N
+            and y.shape == b.shape and y.numel() % 4 == 0 and not (y.requires_grad or b.requires_grad) and N.aligned(y, b):
         out = torch.empty((2 * y.shape[0],) + tuple(y.shape[1:]), dtype=y.dtype, device=y.device)
         N.call("sei_stack_axpy", y.data_ptr(), b.data_ptr(), float(tau), out.data_ptr(), y.numel())
         return out

@@ -154,7 +154,7 @@ def _gemm_call(flops, entry, *args):
 def gemm(A, Bm, M, Nn, K, ta, tb, epi, out=None, bias=None, R1=None, R2=None, D2=None, allow_splitk=True):
     if out is None:
         out = torch.empty((M, Nn), dtype=torch.float32, device=A.device)
-    if get_compute_dtype() == "bf16x3" and _x3_ok(A, Bm, M, Nn, K, ta, tb, epi):
+    if get_compute_dtype() == "bf16x3" and _x3_ok(A, Bm, M, Nn, K, ta, tb, epi, out, R1, D2):
         return gemm_x3(A, Bm, M, Nn, K, ta, tb, epi, out, bias, R1, R2, D2)
     _gemm_call(2.0 * M * Nn * K, _GEMM_ENTRY[get_compute_dtype()] or "sei_gemm_f32_ex", A.data_ptr(), Bm.data_ptr(), out.data_ptr(), M, Nn, K,
                ta, tb, epi, N.ptr(bias), N.ptr(R1), N.ptr(R2), N.ptr(D2), 1, 0, 0, 0, int(allow_splitk))
@@ -168,12 +168,14 @@ _JOINT_SPLIT = None      # (B1, B2) while one backward pass serves the step's tw
 # and slabs by tile ordinal alone, so two launches in flight at once must never share one: a workspace belongs to ONE
 # (device, stream) -- launches on a stream are a chain. Eager launches find theirs in a small registry (created on the
 # stream's first eager use; the least recently used one is dropped when a device has SPLITK_WS_STREAMS of them). A stream
-# that is CAPTURING and has none gets none (its 256-MiB zero fill would be replayed with the graph): those launches take
-# the float-atomics path (sei_gemm_bf16nt / _colsum). graphs.GraphedLossStep therefore warms up and captures on one side
-# stream with a workspace OF ITS OWN (`own_splitk_workspace` ... `release_splitk_workspace`: registered for that stream
-# while the step is being built, kept alive by the graph's owner afterwards): its replays -- serialised by the graph
-# itself -- never share it with anybody, whatever stream they are launched from, and torch handing the same pooled stream
-# to somebody else later cannot alias it. SEI_SPLITK_WS_MIB = 0 switches the workspace off everywhere (round-1..5 path).
+# that is CAPTURING gets none unless it OWNS one (the graph bakes the pointer in, and a registry workspace may be dropped by
+# the LRU or replaced by own_splitk_workspace on the same pooled stream handle while the graph lives; replays would then
+# write slabs and tickets into freed memory): those launches take the float-atomics path (sei_gemm_bf16nt / _colsum).
+# graphs.GraphedLossStep therefore warms up and captures on one side stream with a workspace OF ITS OWN
+# (`own_splitk_workspace` ... `release_splitk_workspace`: registered for that stream while the step is being built, kept
+# alive by the graph's owner afterwards): its replays -- serialised by the graph itself -- never share it with anybody,
+# whatever stream they are launched from, and torch handing the same pooled stream to somebody else later cannot alias it.
+# SEI_SPLITK_WS_MIB = 0 switches the workspace off everywhere (round-1..5 path).
 SPLITK_WS_MIB = int(os.environ.get("SEI_SPLITK_WS_MIB", "256"))
 SPLITK_WS_STREAMS = 4
 SPLITK_COUNTER_BYTES = 16 << 10
@@ -189,14 +191,14 @@ def _splitk_key(device):
 
 def splitk_workspace(device):
     """(pointer, bytes) of the split-K workspace of (`device`, its current stream), or (None, 0): switched off, or the
-    stream is capturing without one."""
+    stream is capturing without a workspace of its own (own_splitk_workspace)."""
     if SPLITK_WS_MIB <= 0:
         return None, 0
     key = _splitk_key(device)
+    if torch.cuda.is_current_stream_capturing() and not getattr(_SPLITK_WS.get(key), "_sei_owned", False):
+        return None, 0
     ws = _SPLITK_WS.pop(key, None)
     if ws is None:
-        if torch.cuda.is_current_stream_capturing():
-            return None, 0
         mine = [k for k in _SPLITK_WS if k[0] == key[0]]
         if len(mine) >= SPLITK_WS_STREAMS:
             del _SPLITK_WS[mine[0]]              # (freed in stream order by the caching allocator: its launches are queued)
@@ -213,6 +215,7 @@ def own_splitk_workspace(device):
         return None
     key = _splitk_key(device)
     ws = _SPLITK_WS[key] = torch.zeros(SPLITK_WS_MIB << 20, dtype=torch.uint8, device=f"cuda:{key[0]}")
+    ws._sei_owned = True                         # (the only kind splitk_workspace hands to a capturing stream)
     return ws
 
 
@@ -262,6 +265,9 @@ def gemm_nt16(A16, B16, M, Nn, K, epi, out32=None, out16=None, bias=None, R1=Non
         B1, B2 = _JOINT_SPLIT
         M1 = M * B1 // (B1 + B2)
         if 0 < M1 < M and M1 % 8 == 0 and (M - M1) % 8 == 0:
+            if A16.dim() != 2 or A16.shape[0] != M:      # (rows are sliced below: a flat or reshaped operand would move by
+                raise ValueError(                      # elements, not rows -- gemm_x3 hands its planes over as (M, K))
+                    f"gemm_nt16 under joint_rows: A16 must be an (M, K) matrix with M = {M}, got {tuple(A16.shape)}")
             # an epilogue operand is cut with the rows when it is per-row data: an (M, Nn) matrix in any view with M * Nn
             # elements, or BIAS_ROWSCALE's M-vector -- never by a leading dimension that happens to equal M
             def cut(t, lo, hi):
@@ -312,13 +318,16 @@ def gemm_nt16(A16, B16, M, Nn, K, epi, out32=None, out16=None, bias=None, R1=Non
 # launches accumulate into the float32 result, small terms first; additive epilogues (bias, residuals, the running
 # gradient) ride on the first launch, GELU / GELU' follow as element-wise passes.
 # ---------------------------------------------------------------------------------------------
-def _x3_ok(A, Bm, M, Nn, K, ta, tb, epi):
-    """Shapes sei_gemm_bf16nt takes (K % 8, 16-byte rows of the reduction-major operands); anything else -- the 3-channel
-    ends of the network never come here -- stays on the float32 GEMM."""
+def _x3_ok(A, Bm, M, Nn, K, ta, tb, epi, out=None, R1=None, D2=None):
+    """Shapes sei_gemm_bf16nt takes (K % 8, 16-byte rows of the reduction-major operands) and operands the float4 passes
+    around it take (sei_split_bf16x2 / x3 read A and Bm, sei_gelu_f32 / sei_mul_dgelu_f32 out with D2 / R1: 16-byte
+    aligned); anything else -- the 3-channel ends of the network never come here -- stays on the float32 GEMM."""
     if not (A.is_cuda and A.dtype == torch.float32 and Bm.dtype == torch.float32 and K % 8 == 0 and Nn % 4 == 0):
         return False
     if (ta and M % 8) or (not tb and Nn % 8) or A.numel() % 4 or Bm.numel() % 4 or not A.is_contiguous() \
             or not Bm.is_contiguous():
+        return False
+    if not N.aligned(A, Bm, out, R1 if epi == EPI_MUL_DGELU else None, D2 if epi == EPI_BIAS_GELU else None):
         return False
     return epi in (EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_MUL_DGELU, EPI_ACCUM, EPI_BIAS_ROWSCALE)
 
@@ -354,7 +363,10 @@ def gemm_x3(A, Bm, M, Nn, K, ta, tb, epi, out, bias=None, R1=None, R2=None, D2=N
         N.call("sei_split_bf16x3", Bm.data_ptr(), b3.data_ptr(), Bm.numel(), 1)
         gemm_nt16(a3, b3, M, Nn, 3 * K, EPI_ACCUM, out32=out, a_rmajor=True, b_rmajor=True, flops=2.0 * M * Nn * K)
         return out
-    a2, b2 = split_x2(A).view(2, -1), split_x2(Bm).view(2, -1)
+    # each plane as the 2-D matrix gemm_nt16 reads ((K, M) / (K, N) when reduction-major): under joint_rows it slices A's
+    # planes by rows
+    a2 = split_x2(A).view(2, -1)[:, :M * K].unflatten(1, (K, M) if arm else (M, K))
+    b2 = split_x2(Bm).view(2, -1)[:, :Nn * K].unflatten(1, (K, Nn) if brm else (Nn, K))
     (a_hi, a_lo), (b_hi, b_lo) = a2, b2
     third = 2.0 * M * Nn * K / 3.0                    # (algorithmic FLOPs are booked once over the three launches)
     first = {EPI_BIAS_GELU: EPI_BIAS, EPI_MUL_DGELU: EPI_NONE}.get(epi, epi)

@@ -148,6 +148,9 @@ class _Axpy(torch.autograd.Function):
         if a.shape != b.shape:
             raise ValueError("axpy: shape mismatch")
         ctx.alpha = alpha
+        # (sei_axpy reads and writes float4: an operand at a storage offset off the 16-byte grid is staged in a fresh
+        # allocation first -- the same launch, the same bits)
+        a, b = (t if N.aligned(t) else t.clone() for t in (a, b))
         out = torch.empty_like(a)
         N.call("sei_axpy", a.data_ptr(), b.data_ptr(), alpha, out.data_ptr(), a.numel())
         return out

@@ -685,3 +685,15 @@ def test_noise2inverse_glue_matches_reference_golden(golden):
     tr = datasets.TrainingDataset(Pairs(), phys, css=False, noise2inverse=True, prepare_training_pairs=lambda a, b: (a, b),
                                   _HOTFIX=False)
     assert tr[0][1].shape == (3, 9, 7) and tr.noise2inverse
+
+
+def test_alignment_predicate_of_the_float4_kernels():
+    """_native.aligned: the predicate the host layer routes on before sei_concat2_f32 / sei_scale_dev_f32 / sei_stack_axpy /
+    sei_axpy / sei_split_bf16x2 (16-byte aligned operands); None is skipped, one misaligned operand is enough to refuse."""
+    import _native as N
+    base = torch.zeros(64 + 16)
+    assert base.data_ptr() % 16 == 0
+    assert N.aligned(base, None, base[4:], base[8:]) and N.aligned()
+    for k in (1, 2, 3, 5):
+        assert not N.aligned(base[k:]) and not N.aligned(base, base[k:])
+    assert N.aligned(base[2:], to=8) and not N.aligned(base[1:], to=8)

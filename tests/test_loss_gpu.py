@@ -1097,6 +1097,55 @@ def test_fused_step_draws_are_torch_generator_draws(B, S, margin):
     assert same_normals(got["b"], second_ref["b"]) and same_normals(got["noise"], second_ref["noise"])
 
 
+@pytest.mark.parametrize("side", ["largest_fused", "smallest_unfused"])
+def test_step_draws_at_the_edge_of_the_fused_regime(side):
+    """sei_proposed_draws reproduces torch's Philox stream only while torch draws one element per thread
+    (numel <= sei_proposed_draws_max_numel()). At the largest 48 x 48 batch inside that limit the fused launch serves the
+    draws and gives torch's numbers; one image more and `draw` / `draw_into` must be torch's own calls -- the same numbers
+    bit for bit, the generator left at the same offset."""
+    import _native as N
+    import physics
+    import transforms
+    from losses import get_loss
+    from losses.sure import draw_probe
+    S, margin = 48, 6
+    limit = N.lib().sei_proposed_draws_max_numel()
+    B = limit // (3 * S * S) + (side == "smallest_unfused")
+    y = torch.empty(B, 3, S, S, device="cuda")
+    assert (y.numel() <= limit) == (side == "largest_fused") and y.numel() % 4 == 0
+    T = transforms.ScalingTransform(kind="padded", antialias=False)
+    torch.cuda.manual_seed(4321)
+    torch.rand(5, device="cuda")
+    b_ref = draw_probe(y, margin)
+    rate_ref, center_ref = T.sample(B, y.device, y.dtype)
+    noise_ref = torch.randn_like(y)
+    after_ref = torch.rand(3, device="cuda")
+    args = ref_args()
+    lf = get_loss(args, physics.get_physics(args, "cuda")).loss
+    lf.sure.margin, lf.sure.cropped_div = margin, True
+    fused = side == "largest_fused"
+    assert lf._fused_draws_ok(y) == fused
+    for into in (False, True):
+        torch.cuda.manual_seed(4321)
+        torch.rand(5, device="cuda")
+        if into:
+            got = {"b": torch.zeros_like(y), "rate": torch.empty(B, device="cuda"),
+                   "center": torch.empty((B, 1, 1, 2), device="cuda"), "noise": torch.empty_like(y)}
+            assert lf.draw_into(got, y)
+        else:
+            got = lf.draw(y)
+        after = torch.rand(3, device="cuda")
+        assert torch.equal(after, after_ref), into
+        assert torch.equal(got["rate"], rate_ref) and torch.equal(got["center"], center_ref), into
+        assert torch.equal(got["b"] == 0, b_ref == 0), into
+        if fused:
+            # (this build's logf / sincosf may differ from ATen's by an ulp: test_fused_step_draws_are_torch_generator_draws)
+            for k, ref in (("b", b_ref), ("noise", noise_ref)):
+                assert float((got[k] == ref).float().mean()) >= 0.98 and torch.allclose(got[k], ref, rtol=4e-6, atol=4e-6), k
+        else:
+            assert torch.equal(got["b"], b_ref) and torch.equal(got["noise"], noise_ref), into
+
+
 def test_crop_pair_on_the_gpu_vs_reference_golden(golden):
     """G14 (src/crop.py run by its own code): the product's crop.CropPair -- forward, and draw_offsets + write_y (the
     sei_crop_window launch a captured step uses) -- on the GPU, same CPU seeds: the same elements in the same places."""

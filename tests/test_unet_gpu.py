@@ -721,11 +721,7 @@ def test_split_bf16_gemm_against_float64(ops, M, N, K):
         ops.set_compute_dtype(prev)
 
 
-@pytest.mark.parametrize("same_stream", [False, True])
-def test_splitk_gemm_inside_hipgraph(ops, same_stream):
-    """A split-K GEMM replayed from a captured graph must not accumulate stale sums. same_stream: warm-up and capture on
-    one side stream, so the launch meets its (device, stream) slab workspace (what graphs.GraphedLossStep does); otherwise
-    the capturing stream has no workspace yet and the launch takes the zero-fill + float-atomics path."""
+def _splitk_gemm_replayed_from_a_graph(ops, same_stream):
     gen = torch.Generator().manual_seed(5)
     M, N, K = 2304, 128, 512                      # 18 tiles, long K: the split-K path
     A = torch.randn((M, K), generator=gen).bfloat16().cuda()
@@ -735,18 +731,40 @@ def test_splitk_gemm_inside_hipgraph(ops, same_stream):
     side = torch.cuda.Stream()
     ops._SPLITK_WS.pop((0, side.cuda_stream), None)       # (torch hands out pooled streams: forget an earlier user's)
     side.wait_stream(torch.cuda.current_stream())
+    ws = None
     with torch.cuda.stream(side if same_stream else torch.cuda.current_stream()):
+        if same_stream:
+            ws = ops.own_splitk_workspace("cuda:0")                    # kept alive by this test for as long as the graph
         ops.gemm_nt16(A, Bm, M, N, K, ops.EPI_NONE, out32=out)          # warm up outside capture
     torch.cuda.synchronize()
     assert ((0, side.cuda_stream) in ops._SPLITK_WS) == same_stream
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        assert (ops.splitk_workspace("cuda:0")[0] is not None) == same_stream
-        ops.gemm_nt16(A, Bm, M, N, K, ops.EPI_NONE, out32=out)
+    try:
+        with torch.cuda.graph(graph, stream=side):
+            handed = ops.splitk_workspace("cuda:0")
+            ops.gemm_nt16(A, Bm, M, N, K, ops.EPI_NONE, out32=out)
+    finally:
+        ops.release_splitk_workspace("cuda:0", side, ws)
+    assert handed == ((ws.data_ptr(), ws.numel()) if same_stream else (None, 0))
     for _ in range(3):
         graph.replay()
         torch.cuda.synchronize()
         assert relerr(out, ref) < 3e-6
+
+
+@pytest.mark.parametrize("same_stream", [False])
+def test_splitk_gemm_inside_hipgraph(ops, same_stream):
+    """A split-K GEMM replayed from a captured graph must not accumulate stale sums: the capturing stream has no workspace
+    and the launch takes the zero-fill + float-atomics path. (Warm-up and capture on one stream that owns its workspace:
+    test_splitk_gemm_inside_hipgraph_with_its_own_workspace.)"""
+    _splitk_gemm_replayed_from_a_graph(ops, same_stream)
+
+
+def test_splitk_gemm_inside_hipgraph_with_its_own_workspace(ops):
+    """Warm-up and capture on one side stream with a slab workspace of its own (own_splitk_workspace ...
+    release_splitk_workspace, what graphs.GraphedLossStep does): the capture is handed exactly that workspace -- never a
+    registry one the LRU could free while the graph lives -- and replays stay within 3e-6 of float64."""
+    _splitk_gemm_replayed_from_a_graph(ops, True)
 
 
 def test_splitk_workspaces_belong_to_one_stream_each(ops):
