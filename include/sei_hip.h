@@ -194,6 +194,14 @@ int sei_mse_loss(const float *a, const float *b, size_t n, float grad_scale, flo
  * Y = 0.299 R + 0.587 G + 0.114 B, torchmetrics PSNR with data_range 1): out1[0] = sum over the npix pixels of
  * (Y(a) - Y(b))^2 for planar RGB images a, b of shape (3, npix). `work` holds SEI_REDUCE_BLOCKS floats. */
 int sei_luma_sqerr(const float *a, const float *b, size_t npix, float *out1, float *work, void *stream);
+/* Luma SSIM of the evaluation step (reference src/metrics.py:15-18: kornia's Y as above, then torchmetrics
+ * structural_similarity_index_measure with its defaults and data_range 1): out[i] = the mean over the (H-10) x (W-10)
+ * windows that lie inside the image of the SSIM of Y(a[i]) and Y(b[i]) under the 11 x 11 Gaussian window of sigma 1.5
+ * (torchmetrics reflect-pads by 5 and crops 5: the two cancel). a, b: `batch` planar RGB images (3, H, W), contiguous,
+ * 4-byte aligned; H, W >= 11. `work` holds sei_ssim_luma_work_floats(batch, H, W) floats (0 = arguments refused).
+ * Deterministic: no atomics; an image's result does not depend on the batch it is in. */
+int sei_ssim_luma(const float *a, const float *b, int batch, int H, int W, float *out, float *work, void *stream);
+size_t sei_ssim_luma_work_floats(int batch, int H, int W);
 
 /* ---------------------------------------------------------------------------------------------
  * U-Net (src/models/convolutional.py), NHWC activations ("rows" = B*H*W pixels of C channels).

@@ -7,19 +7,20 @@ the reference's (same keys), so checkpoints interchange.
 In scope: kind "Proposed" with architecture "Convolutional" (the in-tree U-Net) or "Transformer" (the
 reference's default: deepinv's SwinIR with the arguments at src/models/__init__.py:51-74, rebuilt in
 models/swinir.py from the published architecture -- deepinv is not part of the reference tree, parity
-unpinned), and the trivial "Identity". The test-time baselines (DIP, PnP, BM3D, DiffPIR, DPS, TV, ...)
-raise a clear error instead of silently running something else.
+unpinned), the trivial "Identity" and "InverseFilter", and the bicubic "Upsample" baseline. The other test-time
+baselines (DIP, PnP, BM3D, DiffPIR, DPS, TV) raise a clear error instead of silently running something else.
 """
 from os import environ
 
 from torch import nn
 from torch.nn import Module
 
+from physics import _bands
+from physics._ops import SeparableResampleOp, apply_linear
 from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
 
-_OUT_OF_SCOPE = ("DeepImagePrior", "PlugAndPlay", "BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS", "TV",
-                 "Upsample")
+_OUT_OF_SCOPE = ("DeepImagePrior", "PlugAndPlay", "BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS", "TV")
 
 
 class Identity(Module):
@@ -36,6 +37,22 @@ class InverseFilter(Module):
 
     def forward(self, y):
         return self.physics.A_dagger(y)
+
+
+class Upsample(Module):
+    """The super-resolution baseline (reference src/models/upsample.py): F.interpolate(y, scale_factor=factor,
+    mode="bicubic") -- align_corners False, no antialias, no clamp -- as the separable banded resampler over the plain
+    bicubic matrices (sei_resample_sepband). No parameters: its state dict is empty."""
+
+    def __init__(self, factor):
+        super().__init__()
+        if factor is None:
+            raise ValueError("model kind 'Upsample' upsamples by the super-resolution factor: give --sr_factor")
+        self.factor = factor
+        self._op = SeparableResampleOp(lambda n: _bands.plain_bicubic_matrix(n, factor))
+
+    def forward(self, y):
+        return apply_linear(self._op, y.contiguous())
 
 
 class ProposedModel(Module):
@@ -78,6 +95,8 @@ class Model(Module):
             self.model = Identity()
         elif kind == "InverseFilter":
             self.model = InverseFilter(physics=physics)
+        elif kind == "Upsample":                              # reference :137-138: by sr_factor whatever the task
+            self.model = Upsample(factor=sr_factor)
         elif kind in _OUT_OF_SCOPE:
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
                                       "hot path this build implements")

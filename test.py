@@ -6,11 +6,13 @@
 
 For every test pair: x_hat = model(y) under no_grad (the same HIP forward as training, any image size), then
 quantise to 8 bits and clamp x, y, x_hat (reference :140-148), PSNR on the luma channel (src/metrics.py), and
-the reference's summary lines. In scope: the Proposed model family, `--dataset div2k | single_image | synthetic`
-or a directory of PNG measurements, `--save_images`, `--save_psf`, `--indices`, `--print_all_metrics`,
-`--noise2inverse` (src/noise2inverse.py's sliced evaluation around the same backbone) and `--r2r`.
-Out of scope and refused: DIP / PnP / BM3D / DiffPIR / DPS / TV baselines; SSIM and LPIPS are
-printed as nan (torchmetrics / pyiqa are not rebuilt).
+the reference's summary lines. In scope: the Proposed model family and the Identity / InverseFilter / bicubic Upsample
+kinds, `--dataset div2k | single_image | synthetic` or a directory of PNG measurements, `--save_images`, `--save_psf`,
+`--indices`, `--print_all_metrics`, `--noise2inverse` (src/noise2inverse.py's sliced evaluation around the same
+backbone) and `--r2r`. `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
+`SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. LPIPS always prints nan (pyiqa and its
+pretrained weights are not rebuilt). Out of scope and refused: DIP / PnP / BM3D / DiffPIR / DPS / TV baselines
+(SURVEY section 2).
 """
 import os
 import sys
@@ -50,6 +52,7 @@ def build_parser():
     flag("--SyntheticDataset__deterministic_measurements", action=BooleanOptionalAction, default=True)
     flag("--memoize_gt", action=BooleanOptionalAction, default=False)
     flag("--compute_dtype", choices=["f32", "bf16", "bf16x3"], default="f32")          # build-side addition
+    flag("--ssim", action="store_true")                                                  # build-side addition
     return parser
 
 
@@ -133,7 +136,7 @@ def main(argv=None):
         y = quantize_and_clamp(y)
         x_hat = quantize_and_clamp(x_hat)
         if x is not None:
-            psnr_val, ssim_val, lpips_val = compute_metrics(x.squeeze(0), x_hat.squeeze(0))
+            psnr_val, ssim_val, lpips_val = compute_metrics(x.squeeze(0), x_hat.squeeze(0), ssim=args.ssim)
             psnr_list.append(psnr_val)
             ssim_list.append(ssim_val)
             lpips_list.append(lpips_val)
