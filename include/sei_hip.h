@@ -36,7 +36,7 @@ extern "C" {
  * ctypes stub for each at its reference call site); names, argument meaning and error behaviour are kept across ABI
  * versions:
  *   sei_abi_version, sei_build_target
- *   physics      sei_blur_sep_circ, sei_blur_dense_circ, sei_resample_sepband
+ *   physics      sei_blur_sep_circ, sei_blur_dense_circ, sei_resample_sepband, sei_circ_filter_sep
  *   EI transform sei_scale_resample_fwd, sei_scale_resample_bwd
  *   loss terms   sei_axpy, sei_sure_terms, sei_mse_terms
  *   U-Net (f32)  sei_conv3x3_fwd, sei_conv3x3_bwd_weight, sei_dwconv7_fwd, sei_dwconv7_bwd_weight (+ _workspace),
@@ -49,7 +49,9 @@ extern "C" {
  * kernels: they may change with SEI_ABI_VERSION.
  * --------------------------------------------------------------------------------------------- */
 
-/* ABI version of this header; sei_abi_version() returns the value the library was built with. */
+/* ABI version of this header; sei_abi_version() returns the value the library was built with. Adding an entry point
+ * is backward compatible and does not change it: sei_circ_filter_sep joined version 12 that way (a binding written
+ * against an earlier 12 keeps working; one that needs the new symbol checks for it by name). */
 #define SEI_ABI_VERSION 12
 int sei_abi_version(void);
 /* Fills name[0..n) with the gfx target the code objects were built for ("gfx950"). */
@@ -82,6 +84,26 @@ int sei_blur_sep_circ(const float *x, float *y, const float *tv, const float *th
 /* Non-separable kernels (loaded from a file, src/physics/__init__.py:20-22): k is (kv,kh) row-major. */
 int sei_blur_dense_circ(const float *x, float *y, const float *k, int kv, int kh, int planes,
                         int H, int W, int transpose, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Physics: separable dense circular filter  y[p] = C_v * x[p] * C_h^T  with full circulants
+ *   C_v[i][r] = cv[(i - r) mod H],  C_h[c][j] = ch[(c - j) mod W]
+ * given by their first columns cv (H floats) and ch (W floats), device pointers.
+ * Replaces CTLikeFilter.A / A_dagger, src/physics/ct_like_filter.py:10-18 (filter1d along H then W; each filter1d,
+ * :20-39, is irfft(rfft(x) * otf), i.e. multiplication by a real SYMMETRIC circulant whose first column the caller
+ * builds on the host), and one filter1d alone when the other axis gets the identity column {1, 0, ..., 0}.
+ * There is no transposed form and no `transpose` argument: with symmetric circulants the operator is its own
+ * adjoint, so the autograd backward of a call is the same call. (First columns that are not symmetric are applied as
+ * given, as the formula above says.)
+ * One launch, no intermediate in global memory: one workgroup per (plane, strip of 32 output columns); the row pass
+ * result stays in LDS until the column pass has consumed it. Each output keeps four partial sums per pass.
+ * Any H, W >= 1. SEI_ERR_TOO_LARGE when the workgroup's tiles exceed LDS (160 KiB): 512 x 512 fits (137 KiB), the
+ * bound is 136 * (H + W) + 1 KiB <= 160 KiB up to the rounding of the extents to 4 / 8 / 32.
+ * The one piece of state behind this entry point: above 64 KiB of LDS the kernel's dynamic-LDS allowance is raised once
+ * per device (hipFuncSetAttribute, on the first such call; idempotent, one bit per device remembered).
+ * ------------------------------------------------------------------------------------------- */
+int sei_circ_filter_sep(const float *x, float *y, const float *cv, const float *ch, int planes, int H, int W,
+                        void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Physics: separable banded resampling  y[p] = Wv * x[p] * Wh^T.

@@ -31,6 +31,7 @@ SIGNATURES = {
     "sei_build_target": [_c.c_char_p, _I],
     "sei_blur_sep_circ": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sei_blur_dense_circ": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sei_circ_filter_sep": [_P, _P, _P, _P, _I, _I, _I, _P],
     "sei_resample_sepband": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P],
     "sei_scale_params": [_P, _P, _P, _I, _I, _P, _P, _P],
     "sei_scale_resample_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

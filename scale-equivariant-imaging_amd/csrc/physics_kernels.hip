@@ -1,13 +1,21 @@
 // Physics operators and the EI scale transform for gfx950 (MI355X).
 //
-// All three are HBM-streaming stencils on NCHW planar float32 images: each input tile (plus halo) is
-// read once from HBM into LDS, both separable passes run out of LDS, the output is written once.
+// The blur, the resampler and the scale transform are HBM-streaming stencils on NCHW planar float32 images: each input
+// tile (plus halo) is read once from HBM into LDS, both separable passes run out of LDS, the output is written once.
 // Algorithmic bytes per plane: 4*H*W in + 4*Ho*Wo out.
 //
 //   sei_blur_sep_circ / sei_blur_dense_circ : BlurV2.A and its adjoint  (blur/__init__.py:205-227)
 //   sei_resample_sepband                    : Downsampling.A, adjoints, AA prefilter
 //   sei_scale_resample_fwd/bwd              : padded_downsampling_transform (transforms.py:27-83)
+//   sei_circ_filter_sep                     : CTLikeFilter.A / A_dagger / filter1d (physics/ct_like_filter.py:10-39)
+//
+// sei_circ_filter_sep is the dense one of the family: y = C_v x C_h^T with full circulants (every output depends on a
+// whole row and a whole column), 2*H*W*(H+W) flop per plane on the float32 vector units against the same 8*H*W bytes.
+// One launch, one workgroup per (plane, strip of 32 output columns): the row pass result lives in LDS until the column
+// pass has consumed it (see circ_filter_sep_kernel).
 #include "sei_common.h"
+
+#include <atomic>
 
 namespace {
 
@@ -303,6 +311,111 @@ __global__ __launch_bounds__(256) void rotate_nearest_bwd_kernel(const float *__
         atomicAdd(gx + (size_t)c * H * W + src, gy[(size_t)c * H * W + p]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// separable dense circular filter: y = C_v x C_h^T, C[i][j] = c[(i - j) mod n] given by its first column.
+// One workgroup = one (plane, strip of CF_STRIP output columns, full height). LDS, in floats:
+//   s_th  [round_up(W, 32) + W4]   horizontal taps, periodic: s_th[m] = ch[(m - W4) mod W]     (W4 = round_up(W, 4))
+//   s_tv  [round_up(H, 8) + H4]    vertical taps,   periodic: s_tv[m] = cv[(m - H4) mod H]
+//   s_x   [CF_ROWS][xs]            a chunk of CF_ROWS whole rows of x, zero-padded to W4 columns
+//   s_t   [CF_STRIP][ts]           the row pass result, TRANSPOSED (strip column major), zero-padded to H4 rows
+// so that both passes are the same inner product of a zero-padded LDS row with a sliding window of taps (cf_dot), with
+// no modulo in the loop. Row strides xs / ts are n4 + 4 or n4 + 8, whichever is 4 * odd: eight lanes reading one float4
+// each from eight consecutive rows then touch eight different groups of four banks.
+// Row pass: thread = (row of the chunk, 4 strip columns); the 32 lanes of a half-wave share their taps (broadcast) and
+// read 32 different rows. Column pass: thread = (strip column, 8 output rows); lanes run along the strip, so the
+// global stores are 128-byte segments. x is read from global once per strip (the plane stays in L2 after the first).
+// ------------------------------------------------------------------------------------------------
+constexpr int CF_THREADS = 256;
+constexpr int CF_STRIP = 32;
+constexpr int CF_ROWS = 32;
+
+__host__ __device__ inline int cf_stride(int n4) { return n4 + (((n4 >> 2) & 1) ? 8 : 4); }
+
+// out[k] = sum_{j < n4} src[j] * taps[tb + k - j], k < NO. src and taps 16-byte aligned, n4 and tb multiples of 4,
+// tb >= n4. Each output keeps four partial sums (j mod 4), folded pairwise at the end: every FMA of a step of four
+// inputs lands in its own accumulator (no dependent chain inside a step), and the rounding error grows with n / 4.
+template <int NO>
+__device__ __forceinline__ void cf_dot(const float *__restrict__ src, int n4, const float *__restrict__ taps, int tb,
+                                       float (&out)[NO]) {
+    float acc[NO][4];
+    float w[NO + 4];                    // w[m] = taps[tb - jb - 4 + m]
+#pragma unroll
+    for (int k = 0; k < NO; ++k) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.f;
+#pragma unroll
+    for (int q = 0; q < NO / 4; ++q) {
+        const float4 t = *reinterpret_cast<const float4 *>(taps + tb + 4 * q);
+        w[4 + 4 * q] = t.x; w[5 + 4 * q] = t.y; w[6 + 4 * q] = t.z; w[7 + 4 * q] = t.w;
+    }
+#pragma unroll 4
+    for (int jb = 0; jb < n4; jb += 4) {
+        const float4 lo = *reinterpret_cast<const float4 *>(taps + tb - jb - 4);
+        const float4 xv = *reinterpret_cast<const float4 *>(src + jb);
+        w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w;
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+            for (int k = 0; k < NO; ++k) acc[k][jj] = fmaf(xs[jj], w[4 + k - jj], acc[k][jj]);
+#pragma unroll
+        for (int m = NO + 3; m >= 4; --m) w[m] = w[m - 4];
+    }
+#pragma unroll
+    for (int k = 0; k < NO; ++k) out[k] = (acc[k][0] + acc[k][1]) + (acc[k][2] + acc[k][3]);
+}
+
+__global__ __launch_bounds__(CF_THREADS) void circ_filter_sep_kernel(
+    const float *__restrict__ x, float *__restrict__ y, const float *__restrict__ cv, const float *__restrict__ ch,
+    int H, int W, int strips) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int plane = blockIdx.x / strips;
+    const int c0 = (blockIdx.x - plane * strips) * CF_STRIP;
+    const int H4 = (H + 3) & ~3, W4 = (W + 3) & ~3;
+    const int len_h = ((W + CF_STRIP - 1) & ~(CF_STRIP - 1)) + W4, len_v = ((H + 7) & ~7) + H4;
+    const int xs = cf_stride(W4), ts = cf_stride(H4);
+    float *s_th = smem;
+    float *s_tv = s_th + len_h;
+    float *s_x = s_tv + len_v;
+    float *s_t = s_x + CF_ROWS * xs;
+
+    for (int m = tid; m < len_h; m += CF_THREADS) s_th[m] = ch[sei_mod(m - W4, W)];
+    for (int m = tid; m < len_v; m += CF_THREADS) s_tv[m] = cv[sei_mod(m - H4, H)];
+
+    // row pass: s_t[c][i] = sum_j x[i][j] * ch[(c0 + c - j) mod W], a chunk of CF_ROWS rows at a time
+    const float *xp = x + (size_t)plane * H * W;
+    const int rr = tid & 31, cq = 4 * (tid >> 5);
+    for (int r0 = 0; r0 < H4; r0 += CF_ROWS) {
+        __syncthreads();                                   // the previous chunk is consumed (first time: nothing)
+        for (int r = wave; r < CF_ROWS; r += CF_THREADS / 64) {
+            const int i = r0 + r;
+            for (int j = lane; j < W4; j += 64) s_x[r * xs + j] = (i < H && j < W) ? xp[(size_t)i * W + j] : 0.f;
+        }
+        __syncthreads();
+        const int i = r0 + rr;
+        if (i < H4 && c0 + cq < W) {
+            float o[4] = {0.f, 0.f, 0.f, 0.f};             // rows H .. H4-1 of s_t are the column pass's zero padding
+            if (i < H) cf_dot<4>(s_x + rr * xs, W4, s_th, c0 + cq + W4, o);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s_t[(cq + k) * ts + i] = o[k];
+        }
+    }
+    __syncthreads();
+
+    // column pass: y[i][c0 + c] = sum_r cv[(i - r) mod H] * s_t[c][r]
+    const int c = tid & 31;
+    if (c0 + c < W) {
+        float *yp = y + (size_t)plane * H * W + c0 + c;
+        const int nib = (H + 7) >> 3;
+        for (int ib = tid >> 5; ib < nib; ib += CF_THREADS / 32) {
+            float o[8];
+            cf_dot<8>(s_t + c * ts, H4, s_tv, 8 * ib + H4, o);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (8 * ib + k < H) yp[(size_t)(8 * ib + k) * W] = o[k];
+        }
+    }
+}
+
 // pick a tile so that tile + halo fits comfortably in LDS and small images are one tile
 inline void blur_tiles(int H, int W, int kv, int kh, int &th, int &tw) {
     th = H < 64 ? H : 64;
@@ -345,6 +458,50 @@ extern "C" int sei_blur_dense_circ(const float *x, float *y, const float *k, int
     const size_t grid = (size_t)planes * tiles_y * tiles_x;
     hipLaunchKernelGGL(blur_dense_circ_kernel, dim3((unsigned)grid), dim3(BLUR_THREADS), lds, (hipStream_t)stream,
                        x, y, k, kv, kh, sv, sh, transpose ? 1 : 0, H, W, tile_h, tile_w, tiles_y, tiles_x);
+    return sei_launch_status();
+}
+
+// LDS bytes of one circ_filter_sep_kernel workgroup (the layout in the kernel's comment)
+static size_t circ_filter_lds(int H, int W) {
+    const int H4 = (H + 3) & ~3, W4 = (W + 3) & ~3;
+    const size_t len_h = (size_t)((W + CF_STRIP - 1) & ~(CF_STRIP - 1)) + W4, len_v = (size_t)((H + 7) & ~7) + H4;
+    return sizeof(float) * (len_h + len_v + (size_t)CF_ROWS * cf_stride(W4) + (size_t)CF_STRIP * cf_stride(H4));
+}
+
+// A launch with more than 64 KiB of dynamic LDS needs the kernel's allowance raised first. That is done once per device
+// (to the 160 KiB of a CU), on the first such call there -- an eager one, ahead of any capture of the same extent -- and
+// remembered in one bit per device: idempotent, so a race between two first calls only repeats it.
+static std::atomic<unsigned long long> cf_big_lds_devices{0};
+
+static int circ_filter_allow_big_lds() {
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return (int)e;
+    const unsigned long long bit = 1ull << (device & 63);
+    if (cf_big_lds_devices.load(std::memory_order_relaxed) & bit) return 0;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(circ_filter_sep_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    cf_big_lds_devices.fetch_or(bit, std::memory_order_relaxed);
+    return 0;
+}
+
+extern "C" int sei_circ_filter_sep(const float *x, float *y, const float *cv, const float *ch, int planes, int H,
+                                   int W, void *stream) {
+    SEI_REQUIRE(x && y && cv && ch && x != y);
+    SEI_REQUIRE(planes > 0 && H > 0 && W > 0);
+    if (H > (1 << 15) || W > (1 << 15)) return SEI_ERR_TOO_LARGE;
+    const size_t lds = circ_filter_lds(H, W);
+    if (lds > 160 * 1024) return SEI_ERR_TOO_LARGE;
+    const int strips = (int)sei_ceil_div(W, CF_STRIP);
+    const size_t grid = (size_t)planes * strips;
+    if (grid >= ((size_t)1 << 31)) return SEI_ERR_TOO_LARGE;
+    if (lds > 64 * 1024) {
+        const int rc = circ_filter_allow_big_lds();
+        if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(circ_filter_sep_kernel, dim3((unsigned)grid), dim3(CF_THREADS), lds, (hipStream_t)stream, x, y,
+                       cv, ch, H, W, strips);
     return sei_launch_status();
 }
 

@@ -353,6 +353,10 @@ def get_loss(args, physics):
             sure_margin = (max(kernel.shape[-2], kernel.shape[-1]) - 1) // 2
         elif args.task == "sr":
             sure_margin = 2 if args.partial_sure_sr else 0
+        else:
+            # (the reference falls through here and dies on an unbound name, src/losses/__init__.py:212-226)
+            raise ValueError(f"task {args.task!r} has no default SURE margin: pass --sure_margin N, "
+                             "or --no-partial_sure for a margin of 0")
     else:
         assert args.sure_margin is None
         sure_margin = 0

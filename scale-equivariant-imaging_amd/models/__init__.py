@@ -29,7 +29,8 @@ class Identity(Module):
 
 
 class InverseFilter(Module):
-    """The least-squares pseudo-inverse of the physics as a "model" (reference :22-28): physics.A_dagger(y)."""
+    """The pseudo-inverse of the physics as a "model" (reference :22-28): physics.A_dagger(y) -- least squares by conjugate
+    gradients for the blur and the downsampler, the exact inverse filter for CTLikeFilter."""
 
     def __init__(self, physics):
         super().__init__()

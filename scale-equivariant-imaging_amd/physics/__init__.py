@@ -2,7 +2,7 @@
 
 `get_physics(args, device)` returns an object obeying the deepinv LinearPhysics protocol the
 reference's losses, datasets and scripts rely on: A, A_adjoint, __call__ = noise(A(.)), attributes
-noise_model (.sigma), task, filter/kernel or rate, and the literally-named "__manager" attribute
+noise_model (.sigma), task, filter/kernel or rate (CTLikeFilter has neither), and the literally-named "__manager" attribute
 exposing randomly_degrade(x, seed). The arithmetic runs in the HIP kernels of libsei_hip.so.
 """
 from os.path import exists
@@ -12,6 +12,7 @@ import torch
 from rng import fork_rng
 from ._base import GaussianNoise, LinearPhysics
 from .blur import Blur, BlurV2
+from .ct_like_filter import CTLikeFilter
 from .downsampling import Downsampling
 from .kernels import get_kernel
 
@@ -38,8 +39,7 @@ class PhysicsManager:
         elif task == "sr":
             physics = Downsampling(antialias=True, **blueprint[Downsampling.__name__])
         elif task == "invert_a_tomography_like_filter":
-            raise ValueError("task 'invert_a_tomography_like_filter' (CTLikeFilter) is outside the "
-                             "hot path this build implements")
+            physics = CTLikeFilter()
         else:
             raise ValueError(f"Unknown task: {task}")
 

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 import _native as N
-from . import _bands
+from . import _bands, _circulant
 
 
 class _Linear(torch.autograd.Function):
@@ -70,6 +70,43 @@ class CircularBlurOp:
         else:
             N.call("sei_blur_dense_circ", x.data_ptr(), y.data_ptr(), t[0].data_ptr(), kv, kh, planes,
                    H, W, int(transpose))
+        return y
+
+
+# (n, None | inverse, eps, device) -> float32 first column; shared by every CirculantFilterOp. Never evicted: n floats
+# per distinct image extent, and a run sees a handful of extents.
+_CIRCULANT_COLUMNS = {}
+
+
+def _circulant_column(n, inverse, eps, device):
+    """The float32 first column on `device` of one filtered axis, or (inverse None) the identity column."""
+    key = (n, inverse, eps, device)
+    if key not in _CIRCULANT_COLUMNS:
+        if inverse is None:
+            c = np.zeros(n)
+            c[0] = 1.0
+        else:
+            c = _circulant.first_column(n, inverse, eps)
+        _CIRCULANT_COLUMNS[key] = torch.from_numpy(c.astype(np.float32)).to(device).contiguous()
+    return _CIRCULANT_COLUMNS[key]
+
+
+class CirculantFilterOp:
+    """y = C_v x C_h^T with the symmetric circulants of the reference's CTLikeFilter.filter1d
+    (src/physics/ct_like_filter.py:20-39; physics/_circulant.py): `inverse` picks 1/(f+eps) or f+eps, `dims` the image
+    axes filtered (2 = H, 3 = W; an axis left out gets the identity column). The float32 first columns are built once
+    per (extent, device) from the float64 formula and shared between operators. Symmetric, so `transpose` changes
+    nothing."""
+
+    def __init__(self, inverse, eps=1.0, dims=(2, 3)):
+        self.inverse, self.eps, self.dims = bool(inverse), float(eps), tuple(dims)
+
+    def run(self, x, transpose=False, out_hw=None):
+        planes, H, W = _as_planes(x)
+        cv = _circulant_column(H, self.inverse if 2 in self.dims else None, self.eps, x.device)
+        ch = _circulant_column(W, self.inverse if 3 in self.dims else None, self.eps, x.device)
+        y = torch.empty_like(x)
+        N.call("sei_circ_filter_sep", x.data_ptr(), y.data_ptr(), cv.data_ptr(), ch.data_ptr(), planes, H, W)
         return y
 
 

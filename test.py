@@ -4,7 +4,8 @@
     python test.py --device cuda --task deblurring --kernel Gaussian_R2 --ProposedModel__architecture Convolutional \
         --dataset div2k --GroundTruthDataset__datasets_dir ./datasets --weights runs/x/weights.pt
 
-For every test pair: x_hat = model(y) under no_grad (the same HIP forward as training, any image size), then
+For every test pair: x_hat = model(y) under no_grad (the same HIP forward as training, any image size; with --task
+invert_a_tomography_like_filter up to the extents sei_circ_filter_sep holds in LDS, about 560 per axis), then
 quantise to 8 bits and clamp x, y, x_hat (reference :140-148), PSNR on the luma channel (src/metrics.py), and
 the reference's summary lines. In scope: the Proposed model family and the Identity / InverseFilter / bicubic Upsample
 kinds, `--dataset div2k | single_image | synthetic` or a directory of PNG measurements, `--save_images`, `--save_psf`,

@@ -9,7 +9,7 @@ arithmetic is exercised by the goldens below except `adjoint_function`, which is
 `torch.autograd.functional.vjp` (flagged "vjp" in the fixture names).
 
 What is written is DATA ONLY: seeded inputs and the outputs the reference produced for them
-(G12 noise2inverse; G13 the in-tree R2R / EI loss; G14 CropPair on batches; G15 the loss layer end to end). The reference cannot travel to the GPU box; these files can.
+(G12 noise2inverse; G13 the in-tree R2R / EI loss; G14 CropPair on batches; G15 the loss layer end to end; G16 CTLikeFilter). The reference cannot travel to the GPU box; these files can.
 
     python tools/gen_golden.py            # writes tests/golden/*.npz + manifest json
 """
@@ -445,6 +445,44 @@ def gen_loss_glue():
         _save(f"g15_loss_glue_{tag}", **arrs)
 
 
+def gen_ct_like_filter():
+    """G16: src/physics/ct_like_filter.py (CTLikeFilter, torch.fft only), loaded by path under the deepinv shell
+    (`LinearPhysics` is only a base-class name there). The reference's own A, A_dagger, filter1d and its autograd, in
+    float64 on float32-representable inputs, plus A in float32 (so a test can print the reference's own float32 error
+    beside the kernel's). Per tag: f32.x, f64.A, f64.Adag, f32.A; except `big`: f32.ct, f64.gA, f64.gAdag (the vjp of A /
+    A_dagger at ct); `rect` and `odd`: f64.f1d_dim2_inv, f64.f1d_dim3_fwd. Three files, each below 1 MiB: the small
+    tags, and the 256 x 256 tag in two halves."""
+    os.makedirs(OUT, exist_ok=True)
+    _install_deepinv_shell()
+    mod = _load_by_path("ref_ct_like_filter", os.path.join(REF_SRC, "physics", "ct_like_filter.py"))
+    phys = mod.CTLikeFilter()
+    tags = {"sq": (2, 3, 48, 48), "rect": (1, 3, 47, 33), "tiny": (1, 1, 1, 5), "odd": (1, 1, 19, 23),
+            "big": (1, 1, 256, 256)}
+    files = {"g16_ct_like_filter": {}, "g16_ct_like_filter_big_a": {}, "g16_ct_like_filter_big_b": {}}
+    for n, (tag, shape) in enumerate(tags.items()):
+        x = _rand(shape, 160 + n)
+        x64 = x.double()
+        out = {f"{tag}.f32.x": _np(x), f"{tag}.f64.A": _np(phys.A(x64)), f"{tag}.f64.Adag": _np(phys.A_dagger(x64)),
+               f"{tag}.f32.A": _np(phys.A(x))}
+        if tag == "big":
+            where = {"big.f32.x": "g16_ct_like_filter_big_a", "big.f64.A": "g16_ct_like_filter_big_a",
+                     "big.f64.Adag": "g16_ct_like_filter_big_b", "big.f32.A": "g16_ct_like_filter_big_b"}
+            for k, v in out.items():
+                files[where[k]][k] = v
+            continue
+        _, ct, gA = _fwd_vjp(phys.A, x64, 170 + n)
+        _, _, gAdag = _fwd_vjp(phys.A_dagger, x64, 170 + n)
+        out[f"{tag}.f32.ct"] = _np(ct).astype(np.float32)
+        assert np.array_equal(out[f"{tag}.f32.ct"].astype(np.float64), _np(ct))
+        out[f"{tag}.f64.gA"], out[f"{tag}.f64.gAdag"] = _np(gA), _np(gAdag)
+        if tag in ("rect", "odd"):
+            out[f"{tag}.f64.f1d_dim2_inv"] = _np(phys.filter1d(x64, dim=2, inverse=True))
+            out[f"{tag}.f64.f1d_dim3_fwd"] = _np(phys.filter1d(x64, dim=3, inverse=False))
+        files["g16_ct_like_filter"].update(out)
+    for name, arrs in files.items():
+        _save(name, **arrs)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     _install_deepinv_shell()
@@ -818,9 +856,12 @@ if __name__ == "__main__":
         gen_crop()
     elif sys.argv[1:] == ["--only", "g15"]:
         gen_loss_glue()
+    elif sys.argv[1:] == ["--only", "g16"]:
+        gen_ct_like_filter()
     else:
         main()
         gen_noise2inverse()
         gen_r2r()
         gen_crop()
         gen_loss_glue()
+        gen_ct_like_filter()

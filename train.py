@@ -16,6 +16,8 @@ step runs in libsei_hip.so. Differences, all build-side and documented in DESIGN
   * `--fused_optimizer` (default on for Adam): one fused Adam kernel over the flat parameter bucket.
   * `--fix_batched_crop`: opt out of the reference's batched-crop padding quirk (crop.py).
   * the per-step `.item()` host sync of the reference is replaced by a device-side running mean.
+  * `--task invert_a_tomography_like_filter` with the default `--partial_sure` needs `--sure_margin N` (or
+    `--no-partial_sure`): the reference has no default margin for this task and stops on an unbound name.
 """
 import csv
 import os
