@@ -9,7 +9,7 @@ hipGraph on ROCm) over static buffers and replays it per step:
     optimizer.step()                    # outside the graph: its bias corrections are host scalars
 
 Inside the graph the 1x1-convolution weight gradients of the step's two model calls are produced by one
-GEMM each that STORES its result (models/_ops.py), so only the small remainder of the gradient bucket is
+GEMM each that STORES its result (models/_wgrad.py), so only the small remainder of the gradient bucket is
 zeroed per step.
 
 What stays outside the graph: the random 48-crop of Loss.forward (two CPU randint draws + a strided
@@ -104,7 +104,7 @@ class GraphedLossStep:
         _ops.weight_grad_views(reset=True, owner=backbone)           # record this model's weight-gradient views only
         _ops.reset_splitk_counters(device)
         # warm-up AND capture on this one stream: the split-K workspace of the GEMMs belongs to a (device, stream), and a
-        # stream that first meets it while capturing gets none (models/_ops.py splitk_workspace)
+        # stream that first meets it while capturing gets none (models/_gemm.py splitk_workspace)
         side = self._capture_stream = torch.cuda.Stream(device=device)
         side.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(side):

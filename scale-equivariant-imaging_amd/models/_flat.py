@@ -98,7 +98,7 @@ class FlatParameterBucket:
         """One memset for the whole model; leaves every p.grad attached to the bucket.
 
         store_weight_grads=True (GraphedLossStep, after `plan_weight_grad_store`): the 1x1-convolution weight
-        gradients are not zeroed -- the step's first launch into each of them stores (models/_ops.py)."""
+        gradients are not zeroed -- the step's first launch into each of them stores (models/_wgrad.py)."""
         ranges = self._sei_zero_ranges if store_weight_grads else None
         if ranges is None:
             self.flat_grads.zero_()
@@ -118,7 +118,7 @@ class FlatParameterBucket:
 
     def plan_weight_grad_store(self, min_numel=1 << 20):
         """After at least one eager step: the parts of the gradient bucket that still need zeroing when the
-        weight gradients recorded by models/_ops.py are stored rather than accumulated. Only gradients of at least
+        weight gradients recorded by models/_wgrad.py are stored rather than accumulated. Only gradients of at least
         `min_numel` elements are stored: a small one costs nothing to zero with its neighbours, while its GEMM is a
         split-K launch whose STORING form needs a zero-fill launch of its own in front."""
         base, esz = self.flat_grads.data_ptr(), self.flat_grads.element_size()

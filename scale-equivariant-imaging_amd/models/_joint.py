@@ -23,7 +23,7 @@ Here the backward pass of both calls runs ONCE, on 3B images:
     mirror the first call (a buffer of another shape) is not cut out: it stays an ordinary autograd graph.
 
 Weight gradients: a layer's backward runs once, so the operands of its weight gradient hold both calls' rows; they are
-handed to models/_ops.weight_grad16 as the two row segments it otherwise merges from two backward functions (same
+handed to models/_wgrad.weight_grad16 as the two row segments it otherwise merges from two backward functions (same
 launches: the stored / Adam-epilogue / streamed forms all see "two pairs of the step's two calls").
 
 SEI_NO_JOINT_BACKWARD=1 switches the mechanism off (A/B runs; the tests compare both).

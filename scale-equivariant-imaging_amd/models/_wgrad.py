@@ -1,0 +1,522 @@
+"""The weight-gradient scheduler: when, and as which launch, the weight gradient of a 1x1 convolution (or a linear
+layer of a Swin block) is issued. The layer functions (models/_ops.py, models/_swin_ops16.py) hand their operand pairs
+to `weight_grad16` / `weight_grad16_group` and their partial sums to `defer_fold`; everything else here is bookkeeping
+per backbone (`WeightGradState`), reached through thin module-level functions.
+"""
+import os
+import weakref
+
+import torch
+
+import _native as N
+from . import _gemm
+from ._gemm import EPI_ACCUM, EPI_NONE, _gemm_call, gemm_mixed, gemm_nt16
+
+# The token-streaming kernels of token_gemm.hip (Swin blocks) against the tiled GEMMs they replace: on unless
+# SEI_SWIN_TILED=1 (tests flip the flag to run the same step on both paths; shapes the streaming kernels do not take --
+# token counts that are not multiples of 64 -- use the tiled ones anyway).
+TOKEN_STREAMING = os.environ.get("SEI_SWIN_TILED") != "1"
+
+# Streamed weight gradients of the shallow levels (csrc/dw_stream.hip): the accumulating weight gradients whose shapes
+# sei_dwstream_bf16_eligible takes -- conv2 / conv3 of the C = 32 and C = 128 blocks, the 1x1 convolutions between the
+# 32-, 128- and 512-channel levels -- are not launched one by one on the tiled GEMM (a 128 x 128 output tile under up to
+# 256 K-splits) but collected, operands kept alive, and issued as ONE job table when the backward pass ends (the engine
+# callback that flushes parked pairs and deferred folds), or at once outside a backward pass. SEI_NO_DWSTREAM=1: the GEMMs.
+DWSTREAM = os.environ.get("SEI_NO_DWSTREAM") != "1"
+
+# Deferred folds. The reducing kernels of a backward pass (LayerNorm parameter gradients, depthwise weight gradients,
+# the LayerNorm epilogue of SwinIR's data-gradient GEMMs) leave per-workgroup partial sums; instead of one ~5-us fold
+# launch behind each of them (52 per U-Net step, ~146 per SwinIR step) the partial sums are kept alive and ONE
+# sei_fold_many launch per <= 40 destinations adds them up when the backward pass ends (the engine callback that also
+# flushes parked weight gradients) -- same slices, same order, launches of one destination one after the other:
+# bit-identical gradients. Outside a backward pass (kernel-level tests calling the helpers directly) nothing is
+# deferred. SEI_NO_DEFERRED_FOLDS=1 restores the fold per launch.
+DEFERRED_FOLDS = os.environ.get("SEI_NO_DEFERRED_FOLDS") != "1"
+
+_NOT_MERGED = {
+    "adam": "fused optimizer step: a weight registered with set_fused_adam did not receive its "
+            "gradient as one merged storing GEMM (different loss / batch / call count than planned)",
+    "direct16": "bf16 gradients written into the exchange buffer: a registered weight did not receive its "
+                "gradient as one merged storing GEMM (different loss / batch / call count than planned)",
+}
+
+
+def colsum16_into(acc, x16):
+    """acc[n] += sum_m x16[m, n]: a bias gradient from the bf16 gradient of the layer's output."""
+    M, Nn = x16.shape
+    N.call("sei_colsum_bf16", x16.data_ptr(), acc.data_ptr(), M, Nn)
+
+
+def _dwstream_ok(grad2d, pairs):
+    """The streamed launch serves this weight gradient (shapes, layouts, pixel counts)."""
+    if not DWSTREAM or not grad2d.is_cuda or grad2d.dim() != 2 or grad2d.dtype != torch.float32 or len(pairs) > 2:
+        return False
+    Np, Kp = grad2d.shape
+    if grad2d.stride(1) != 1:
+        return False
+    for gy, x in pairs:
+        if not (gy.dtype == x.dtype == torch.bfloat16 and gy.is_contiguous() and x.is_contiguous()
+                and gy.dim() == 2 and x.dim() == 2 and gy.shape[1] == Np and x.shape[1] == Kp and gy.shape[0] == x.shape[0]):
+            return False
+    K1 = pairs[0][0].shape[0]
+    K2 = pairs[1][0].shape[0] if len(pairs) == 2 else 0
+    return N.lib().sei_dwstream_bf16_eligible(Np, Kp, Np, Kp, K1, K2) != 0
+
+
+# ---------------------------------------------------------------------------------------------
+# weight gradients of the 1x1 convolutions, merged across the model calls of one step
+#
+# ProposedLoss calls the model twice per step (the fused SURE pass on 2B crops and the EI pass on B); each
+# call's backward used to read-modify-write every weight gradient, which at the deep levels (268 M weights,
+# 1.07 GB of float32 gradient each) is HBM traffic, not arithmetic. Instead the first backward to reach a
+# weight parks its (gy, x) pair, and the second one issues ONE GEMM whose reduction runs over both pairs
+# (sei_gemm_bf16nt_dw2). Pairs still parked when autograd finishes are flushed by an engine callback, so
+# `p.grad` is complete whenever .backward() returns, whoever consumes it.
+#
+# "Store" mode (opt-in, GraphedLossStep): the first launch of a step into a weight gradient stores instead
+# of accumulating, and zero_grad skips those gradients -- valid because the captured step writes every one
+# of them exactly this way on every replay.
+# ---------------------------------------------------------------------------------------------
+class WeightGradState:
+    """The bookkeeping below, PER BACKBONE: model calls of the step, parked pairs, store / fused-Adam / direct-bf16
+    tables. Two models alive in one process (a frozen copy beside the fine-tuned one, two networks trained side by
+    side) each merge and store their own weight gradients. A backbone's state is found from the address of the
+    gradient a backward function writes (`register_gradient_range`: the flat gradient bucket, SwinPack's staging);
+    gradients outside every registered range (kernel-level tests) share the default state. Gradients are known by
+    their data_ptr (`key`)."""
+
+    __slots__ = ("uses", "arrivals", "parked", "written", "store", "store_min", "merge", "flush_queued", "seen",
+                 "flops_per_row", "taps", "bias_of", "merged_ok", "milestone", "milestone_done", "adam", "adam_launched",
+                 "direct16", "direct16_launched", "dwjobs", "folds", "__weakref__")
+
+    def __init__(self):
+        self.uses = 0                   # differentiated model calls of this step (note_forward)
+        self.arrivals = {}              # key -> operand pairs handed in this step
+        self.parked = {}                # key -> (gy16, x16, grad2d), or ("group", key) -> items: waiting for the other call
+        self.written = set()            # keys launched into this step
+        self.store = False              # store mode: a step's first launch into a gradient stores ...
+        self.store_min = 0              # ... when the gradient has at least this many elements
+        self.merge = True               # park and merge across the step's model calls
+        self.flush_queued = False       # the engine callback of the running backward pass is queued
+        self.seen = {}                  # key -> numel of every gradient view since the last weight_grad_views(reset=True)
+        self.flops_per_row = {}         # key -> algorithmic FLOPs per reduction row to book, or None
+        self.taps = {}                  # key -> tap row offsets of a (T, N', K') gradient
+        self.bias_of = {}               # key -> bias gradient whose column sums go with the weight's next launch
+        self.merged_ok = {}             # key -> its last launch was the step's complete gradient in one two-segment GEMM
+        self.milestone = None           # (frozenset of keys, event) or None (set_weight_grad_milestone)
+        self.milestone_done = False
+        self.adam = None                # ({key: (param, exp_avg, exp_avg_sq, shadow)}, hyper) or None (set_fused_adam)
+        self.adam_launched = set()
+        self.direct16 = None            # {key: bf16 view of the exchange buffer} or None (set_direct_bf16_grads)
+        self.direct16_launched = set()
+        self.dwjobs = []                # [(DwStreamJob, operands kept alive, flops)] queued for the streamed launch
+        self.folds = {}                 # destination pointer -> {"meta", "segs"}: deferred folds of the running pass
+
+    # -- the launch decision --------------------------------------------------------------------------------
+    def may_store(self, grad2d):
+        """This launch into grad2d stores instead of accumulating: store mode, the step's first, a gradient large enough
+        to have been left out of zero_grad."""
+        return self.store and grad2d.data_ptr() not in self.written and grad2d.numel() >= self.store_min
+
+    def whole_step(self, segments):
+        """A launch over `segments` row segments carries the step's COMPLETE gradient: both model calls, merged."""
+        return segments == 2 and segments == self.uses
+
+    def launch(self, grad2d, pairs):
+        key = grad2d.data_ptr()
+        store = self.may_store(grad2d)
+        self.written.add(key)
+        try:
+            self._issue(grad2d, pairs, store)
+        finally:
+            self.check_milestone(key)
+
+    def _issue(self, grad2d, pairs, store):
+        key = grad2d.data_ptr()
+        # (weight_grad16(..., bias=): the bias gradient = gy's column sums rides in the streamed launch where that serves
+        # the weight, else it is summed here, one column-sum launch per pair.)
+        bias = self.bias_of.pop(key, None)
+        if bias is not None and (store or not _dwstream_ok(grad2d, pairs)):
+            for gy16, _ in pairs:
+                colsum16_into(bias, gy16)
+            bias = None
+        Np, Kp = grad2d.shape[-2:]
+        (g1, x1), (g2, x2) = pairs if len(pairs) == 2 else (pairs[0], pairs[0])
+        K1, K2 = g1.shape[0], (g2.shape[0] if len(pairs) == 2 else 0)
+        complete = self.whole_step(len(pairs)) and (K1 + K2) % 8 == 0      # ... in rows the dw2 kernels take
+        self.merged_ok[key] = complete
+        table = "adam" if self.adam is not None and key in self.adam[0] else \
+            "direct16" if self.direct16 is not None and key in self.direct16 else None
+        if table is not None:
+            # the update (the bf16 gradient) replaces the stored gradient only when this launch IS the step's whole gradient
+            launched = self.adam_launched if table == "adam" else self.direct16_launched
+            if not (store and complete) or key in launched:
+                raise RuntimeError(_NOT_MERGED[table])
+            launched.add(key)
+            if table == "adam":
+                prm, m1, v1, sh = self.adam[0][key]
+                _gemm_call(2.0 * Np * Kp * (K1 + K2), "sei_gemm_bf16nt_dw2_adam", g1.data_ptr(), g2.data_ptr(), Np,
+                           x1.data_ptr(), x2.data_ptr(), Kp, prm.data_ptr(), m1.data_ptr(), v1.data_ptr(), N.ptr(sh),
+                           self.adam[1].data_ptr(), Np, Kp, K1, K2)
+            else:
+                _gemm_call(2.0 * Np * Kp * (K1 + K2), "sei_gemm_bf16nt_dw2_bf16out", g1.data_ptr(), g2.data_ptr(), Np,
+                           x1.data_ptr(), x2.data_ptr(), Kp, self.direct16[key].data_ptr(), Np, Kp, K1, K2)
+            return
+        taps = self.taps.get(key)
+        if taps is not None:                               # (T, N', K') gradient: every tap in one launch
+            T = grad2d.shape[0]
+            per_row = self.flops_per_row.get(key) or 2.0 * T * Np * Kp
+            if (K1 + K2) % 8 != 0:
+                raise ValueError("weight_grad16 with taps: the reduction length must be a multiple of 8 rows")
+            if TOKEN_STREAMING and not store and Np == 192 and Kp == 192 and T <= N.TOKGRAD_MAX_BLOCKS \
+                    and K1 % 64 == 0 and K2 % 64 == 0 \
+                    and g1.stride(0) == Np and x1.stride(0) == Kp and grad2d.is_contiguous():
+                # 192-channel convolutions (the body of the SwinIR network): the taps are blocks of ONE token-streamed launch --
+                # the same gy rows against the input rows shifted by each tap's offset, every block with its share of the CUs,
+                # the two operands crossing an XCD's L2 once for all nine (sei_tokgrad_bf16_blocks; the tiled kernel re-stages
+                # both operands for every 128 x 128 tile of every tap)
+                blocks = [N.TokGradBlock(g1.data_ptr(), g2.data_ptr(), x1.data_ptr() + 2 * Kp * int(taps[t]),
+                                         x2.data_ptr() + 2 * Kp * int(taps[t]), Np, Kp, 0, 0,
+                                         grad2d.data_ptr() + 4 * t * Np * Kp, Kp) for t in range(T)]
+                arr = (N.TokGradBlock * T)(*blocks)
+                _gemm_call(per_row * (K1 + K2), "sei_tokgrad_bf16_blocks", arr, T, K1, K2)
+                return
+            _gemm_call(per_row * (K1 + K2), "sei_gemm_bf16nt_dw2_taps", g1.data_ptr(), g2.data_ptr(), Np, x1.data_ptr(),
+                       x2.data_ptr(), Kp, grad2d.data_ptr(), Np, Kp, K1, K2, 0 if store else 1, T, taps, Np * Kp)
+            return
+        per_row = self.flops_per_row.get(key) or 2.0 * Np * Kp
+        if not store and self.queue_dwstream(grad2d, pairs, per_row, bias):
+            return
+        assert bias is None
+        if len(pairs) == 2 and (K1 + K2) % 8 == 0:
+            _gemm_call(per_row * (K1 + K2), "sei_gemm_bf16nt_dw2", g1.data_ptr(), g2.data_ptr(), Np,
+                       x1.data_ptr(), x2.data_ptr(), Kp, grad2d.data_ptr(), Np, Kp, K1, K2, 0 if store else 1)
+            return
+        for gy16, x16 in pairs:
+            rows = gy16.shape[0]
+            if rows % 8 == 0:
+                gemm_nt16(gy16, x16, Np, Kp, rows, EPI_NONE if store else EPI_ACCUM, out32=grad2d, a_rmajor=True,
+                          b_rmajor=True, flops=per_row * rows)
+            else:       # a pixel count the LDS-DMA kernel cannot chunk (e.g. 9 bottleneck pixels x batch 2): staged kernel
+                gemm_mixed(gy16, x16, Np, Kp, rows, 1, 0, EPI_NONE if store else EPI_ACCUM, out=grad2d)
+            store = False
+
+    def launch_group(self, segs):
+        """The weight gradients of several layers over the same tokens -- segs: one list of (gy16, x16, grad2d, flops per
+        row) per model call of the step, the layers in the same order -- as ONE token-streamed launch
+        (sei_tokgrad_bf16_blocks: every 192 x 192 block of every gradient on its share of the CUs) when the shapes allow
+        it and every gradient accumulates; one launch per layer otherwise."""
+        first = segs[0]
+        rows = [seg[0][0].shape[0] for seg in segs]
+        blocks, ok = [], TOKEN_STREAMING and len(segs) <= 2 and all(r % 64 == 0 for r in rows)
+        for i, (_, _, grad2d, _) in enumerate(first):
+            key = grad2d.data_ptr()
+            ok = ok and grad2d.dim() == 2 and grad2d.is_contiguous() and grad2d.dtype == torch.float32
+            ok = ok and not self.may_store(grad2d)
+            ok = ok and not (self.adam is not None and key in self.adam[0])
+            ok = ok and not (self.direct16 is not None and key in self.direct16) and key not in self.taps
+            for s, seg in enumerate(segs):
+                gy, x = seg[i][0], seg[i][1]
+                ok = ok and gy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and gy.is_contiguous() and x.is_contiguous()
+                ok = ok and gy.shape == (rows[s], grad2d.shape[0]) and x.shape == (rows[s], grad2d.shape[1])
+            if ok:
+                ok = N.lib().sei_tokgrad_bf16_eligible(grad2d.shape[0], grad2d.shape[1], grad2d.shape[0], grad2d.shape[1],
+                                                       rows[0], rows[1] if len(rows) == 2 else 0) != 0
+            if not ok:
+                break
+            Mo, Ni = grad2d.shape
+            a, b = segs[0][i], segs[-1][i]
+            for gy in range(Mo // 192):
+                for gx in range(Ni // 192):
+                    blocks.append(N.TokGradBlock(a[0].data_ptr(), b[0].data_ptr(), a[1].data_ptr(), b[1].data_ptr(), Mo, Ni,
+                                                 192 * gy, 192 * gx, grad2d.data_ptr() + 4 * (192 * gy * Ni + 192 * gx), Ni))
+        if not ok or len(blocks) > 8:
+            for i, (_, _, grad2d, _) in enumerate(first):
+                self.launch(grad2d, [(seg[i][0], seg[i][1]) for seg in segs])
+            return
+        flops = 0.0
+        for _, _, grad2d, fpr in first:
+            key = grad2d.data_ptr()
+            self.written.add(key)
+            self.merged_ok[key] = self.whole_step(len(segs))
+            flops += (fpr or 2.0 * grad2d.shape[0] * grad2d.shape[1]) * sum(rows)
+        arr = (N.TokGradBlock * len(blocks))(*blocks)
+        try:
+            _gemm_call(flops, "sei_tokgrad_bf16_blocks", arr, len(blocks), rows[0], rows[1] if len(rows) == 2 else 0)
+        finally:
+            for _, _, grad2d, _ in first:
+                self.check_milestone(grad2d.data_ptr())
+
+    def check_milestone(self, key):
+        ms = self.milestone
+        if ms is not None and key in ms[0] and ms[0] <= self.written and not self.milestone_done:
+            # every gradient of the milestone has had its (single, merged) launch of this step
+            if all(self.arrivals.get(k, 0) >= max(self.uses, 1) for k in ms[0]):
+                # a milestone gradient that was only QUEUED for the streamed launch (flush at the end of the backward pass)
+                # must be on the stream before the event that releases it to the reducer
+                if any(job[1][4].data_ptr() in ms[0] for job in self.dwjobs):
+                    self.flush_dwstream()
+                ms[1].record()
+                self.milestone_done = True
+
+    # -- streamed weight gradients (DWSTREAM above) ---------------------------------------------------------
+    def queue_dwstream(self, grad2d, pairs, per_row, bias=None):
+        if not _dwstream_ok(grad2d, pairs):
+            return False
+        Np, Kp = grad2d.shape
+        K1 = pairs[0][0].shape[0]
+        K2 = pairs[1][0].shape[0] if len(pairs) == 2 else 0
+        (g1, x1), (g2, x2) = pairs[0], pairs[-1]
+        job = N.DwStreamJob(g1.data_ptr(), g2.data_ptr(), x1.data_ptr(), x2.data_ptr(), Np, Kp, Np, Kp, grad2d.data_ptr(),
+                            grad2d.stride(0), 0, K1, K2, N.ptr(bias))
+        self.dwjobs.append((job, (g1, x1, g2, x2, grad2d, bias), per_row * (K1 + K2)))
+        if len(self.dwjobs) == N.DWSTREAM_MAX_JOBS or not self.queue_flush():
+            self.flush_dwstream()
+        return True
+
+    def flush_dwstream(self):
+        jobs, self.dwjobs = self.dwjobs, []
+        if not jobs:
+            return
+        arr = (N.DwStreamJob * len(jobs))(*[j[0] for j in jobs])
+        _gemm_call(sum(j[2] for j in jobs), "sei_dwstream_bf16_jobs", arr, len(jobs))   # (the operands in `jobs` live until here)
+
+    # -- deferred folds (DEFERRED_FOLDS above) --------------------------------------------------------------
+    def defer_fold(self, a, b, c, ncol, split, kind, work, offset, groups):
+        if not self.queue_flush():
+            return False
+        key = a.data_ptr()
+        meta = (N.ptr(b), N.ptr(c), int(ncol), int(split), int(kind))
+        job = self.folds.get(key)
+        if job is not None and (job["meta"] != meta or len(job["segs"]) == 3):
+            self.flush_folds()
+            job = None
+        if job is None:
+            if len(self.folds) == N.FOLD_MAX_JOBS:
+                self.flush_folds()
+            job = self.folds[key] = {"meta": meta, "segs": []}       # (flush_folds starts a new table)
+        job["segs"].append((work, work.data_ptr() + 4 * int(offset), int(groups)))
+        return True
+
+    def flush_folds(self):
+        jobs, self.folds = self.folds, {}
+        if not jobs:
+            return
+        arr = (N.FoldJob * len(jobs))()
+        for j, (a_ptr, job) in zip(arr, jobs.items()):
+            b_ptr, c_ptr, ncol, split, kind = job["meta"]
+            j.a, j.b, j.c, j.ncol, j.split, j.kind, j.nseg = a_ptr, b_ptr, c_ptr, ncol, split, kind, len(job["segs"])
+            for k, (_, ptr, groups) in enumerate(job["segs"]):
+                j.part[k] = ptr
+                j.groups[k] = groups
+        N.call("sei_fold_many", arr, len(jobs))           # (the partial-sum tensors in `jobs` live until here)
+
+    # -- the end of the backward pass -----------------------------------------------------------------------
+    def queue_flush(self):
+        """Ask autograd to flush parked pairs when the running backward ends; False outside a backward pass
+        (then nothing may be parked: nobody would flush it)."""
+        if not self.flush_queued:
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(self.flush)
+            except RuntimeError:
+                return False
+            self.flush_queued = True
+        return True
+
+    def flush(self):
+        """Issue every parked weight gradient on its own (no partner arrived), then the streamed jobs and the folds."""
+        self.flush_queued = False
+        parked, self.parked = self.parked, {}
+        for entry in parked.values():
+            if isinstance(entry, list):                    # a parked group (weight_grad16_group)
+                self.launch_group([entry])
+            else:
+                gy16, x16, grad2d = entry
+                self.launch(grad2d, [(gy16, x16)])
+        self.flush_dwstream()
+        self.flush_folds()
+
+
+_DEFAULT_STATE = WeightGradState()
+_RANGES = []                      # [(first byte, end byte, weakref to the WeightGradState)], newest last
+
+
+def state_of(owner=None):
+    """The state of `owner` (a backbone with a flat bucket; created on first use), or the default one."""
+    if owner is None:
+        return _DEFAULT_STATE
+    st = owner.__dict__.get("_sei_dw_state")
+    if st is None:
+        st = owner.__dict__["_sei_dw_state"] = WeightGradState()
+    return st
+
+
+def register_gradient_range(owner, tensor):
+    """Gradients written inside `tensor` (the owner's flat gradient bucket, a staging buffer) belong to `owner`."""
+    lo = tensor.data_ptr()
+    hi = lo + tensor.numel() * tensor.element_size()
+    _RANGES[:] = [r for r in _RANGES if r[2]() is not None and not (r[0] < hi and lo < r[1])]
+    _RANGES.append((lo, hi, weakref.ref(state_of(owner))))
+
+
+def _state_for(ptr):
+    for lo, hi, ref in reversed(_RANGES):
+        if lo <= ptr < hi:
+            st = ref()
+            if st is not None:
+                return st
+    return _DEFAULT_STATE
+
+
+def note_forward(owner=None):
+    """A model call that autograd will differentiate (ConvolutionalModel.forward / SwinIR.forward pass themselves)."""
+    if torch.is_grad_enabled():
+        state_of(owner).uses += 1
+
+
+def begin_step(store=False, store_min=0, owner=None):
+    """Start of a step (zero_grad): nothing parked, no model call counted, no gradient written yet. store: the
+    first launch of the step into a weight gradient of at least store_min elements stores (it was not zeroed)."""
+    st = state_of(owner)
+    st.flush()
+    rec = owner.__dict__.get("_sei_joint") if owner is not None else None
+    if rec is not None:
+        rec.reset()
+    st.uses = 0
+    st.arrivals.clear()
+    st.written.clear()
+    st.milestone_done = False
+    st.store = bool(store)
+    st.store_min = int(store_min)
+
+
+def set_weight_grad_merging(enabled, owner=None):
+    st = state_of(owner)
+    previous, st.merge = st.merge, bool(enabled)
+    return previous
+
+
+def weight_grad_views(reset=False, owner=None):
+    """{data_ptr: numel} of every gradient view written through weight_grad16 since the last reset."""
+    st = state_of(owner)
+    seen = dict(st.seen)
+    if reset:
+        st.seen.clear()
+        st.taps.clear()
+        st.merged_ok.clear()
+        st.flops_per_row.clear()
+    return seen
+
+
+def set_weight_grad_milestone(keys, event, owner=None):
+    """Record `event` on the current stream right after the LAST of the gradients `keys` (data_ptrs) has been
+    launched in a step (GraphedLossStep: an external event inside the captured backward, after which the
+    bottleneck block's gradients -- most of the bucket -- are final and their all-reduce may start)."""
+    state_of(owner).milestone = (frozenset(keys), event) if keys else None
+
+
+def set_fused_adam(table, hyper, owner=None):
+    """Optimizer step inside the weight-gradient GEMM (optim.FlatAdam.fuse_weight_updates): `table` maps the
+    data_ptr of a gradient view to the (param, exp_avg, exp_avg_sq, bf16 shadow or None) views of the same shape,
+    `hyper` is the device array of the step's six Adam scalars. The step's single, merged, storing launch into such a
+    gradient applies the update instead of writing the gradient (sei_gemm_bf16nt_dw2_adam); None switches it off."""
+    st = state_of(owner)
+    st.adam = (dict(table), hyper) if table else None
+    st.adam_launched = set()
+
+
+def set_direct_bf16_grads(table, owner=None):
+    """Several GPUs, bf16-compressed exchange (parallel.FlatGradientReducer): `table` maps the data_ptr of a gradient
+    view to the bf16 view of the exchange buffer with the same shape. The step's single, merged, storing launch into
+    such a gradient writes bf16 there (sei_gemm_bf16nt_dw2_bf16out) and nothing into the float32 bucket, which the
+    reducer then does not cast for those ranges; None switches it off."""
+    st = state_of(owner)
+    st.direct16 = dict(table) if table else None
+    st.direct16_launched = set()
+
+
+def direct_bf16_launches(owner=None):
+    return set(state_of(owner).direct16_launched)
+
+
+def fused_adam_launches(owner=None):
+    """data_ptrs whose update was applied inside a GEMM since set_fused_adam."""
+    return set(state_of(owner).adam_launched)
+
+
+def merged_weight_grads(owner=None):
+    """data_ptrs of the gradients whose last launch carried the step's COMPLETE gradient as one two-segment GEMM (the
+    condition for applying the optimizer step, or writing bf16, in that launch: graphs.GraphedLossStep reads this after
+    its warm-up steps -- a batch whose pixel counts do not add up to a multiple of 8 rows is served by other launches)."""
+    return {k for k, ok in state_of(owner).merged_ok.items() if ok}
+
+
+def flush_weight_grads(owner=None):
+    """Issue every parked weight gradient of `owner` (default state when None) on its own (no partner arrived)."""
+    state_of(owner).flush()
+
+
+def weight_grad16(gy16, x16, grad2d, flops_per_row=None, tap_rows=None, bias=None):
+    """grad (N', K') += gy^T x, gy16 (M, N') and x16 (M, K') bf16 as stored: both read reduction-major.
+    May park the pair until the step's other model call reaches the same weight (see above). flops_per_row: the
+    algorithmic FLOPs per reduction row to book for the roofline leg when the operands are zero-padded (2 N' K').
+    tap_rows (a ctypes int array of T row offsets): grad2d is (T, N', K') and slice t is gy^T x[rows shifted by
+    tap_rows[t]] -- the taps of a 3x3 convolution's weight gradient in one launch (sei_gemm_bf16nt_dw2_taps); x16 is
+    the un-shifted window of a grid with guard rows on both sides."""
+    key = grad2d.data_ptr()
+    st = _state_for(key)
+    st.seen[key] = grad2d.numel()
+    st.flops_per_row[key] = flops_per_row
+    if bias is not None:                   # (M,)-shaped float32 gradient: += gy's column sums, with the weight's launch
+        st.bias_of[key] = bias
+    if tap_rows is not None:
+        st.taps[key] = tap_rows
+    else:
+        st.taps.pop(key, None)              # the address may have belonged to a freed model's tap-major gradient
+    split = _gemm._JOINT_SPLIT
+    if split is not None and tap_rows is None:
+        # one backward pass for the step's two model calls (models/_joint.py): the operands hold both calls' rows -- the
+        # two row segments that two backward functions would otherwise have brought one after the other
+        M1 = gy16.shape[0] * split[0] // (split[0] + split[1])
+        st.arrivals[key] = st.arrivals.get(key, 0) + 2
+        st.launch(grad2d, [(gy16[:M1], x16[:M1]), (gy16[M1:], x16[M1:])])
+        return
+    n = st.arrivals.get(key, 0) + 1
+    st.arrivals[key] = n
+    partner = st.parked.pop(key, None)
+    if partner is not None:
+        st.launch(grad2d, [partner[:2], (gy16, x16)])
+    elif st.merge and n < st.uses and st.queue_flush():
+        st.parked[key] = (gy16, x16, grad2d)
+    else:
+        st.launch(grad2d, [(gy16, x16)])
+
+
+def weight_grad16_group(items):
+    """weight_grad16 for several layers whose operands cover the SAME tokens (the four linear layers of a Swin block):
+    items = [(gy16, x16, grad2d, flops_per_row)]. Parked and merged across the step's model calls like single pairs; the
+    launch is one token-streamed kernel for all of them (WeightGradState.launch_group)."""
+    items = list(items)
+    head = items[0][2].data_ptr()
+    st = _state_for(head)
+    for gy16, x16, grad2d, fpr in items:
+        key = grad2d.data_ptr()
+        st.seen[key] = grad2d.numel()
+        st.flops_per_row[key] = fpr
+        st.taps.pop(key, None)
+        st.arrivals[key] = st.arrivals.get(key, 0) + 1
+    n = st.arrivals[head]
+    gkey = ("group", head)
+    partner = st.parked.pop(gkey, None)
+    if partner is not None:
+        st.launch_group([partner, items])
+    elif st.merge and n < st.uses and st.queue_flush():
+        st.parked[gkey] = items
+    else:
+        st.launch_group([items])
+
+
+def defer_fold(a, b, c, ncol, split, kind, work, offset, groups):
+    """Register `work[offset:]` ([groups][ncol] partial sums, kept alive here) to be folded into a (| b | c) when the
+    running backward pass ends. False: not deferred (switched off / no backward pass running) -- the caller folds."""
+    return DEFERRED_FOLDS and _state_for(a.data_ptr()).defer_fold(a, b, c, ncol, split, kind, work, offset, groups)

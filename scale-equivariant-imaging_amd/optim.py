@@ -58,7 +58,7 @@ class FlatAdam(torch.optim.Optimizer):
         gradient round trip and 26 of Adam's 30 bytes per parameter move into that GEMM's epilogue, under its MFMA
         work). `step()` then covers the rest of the bucket; `prepare_step()` must run before every captured step so
         that the device scalars the epilogue reads belong to the step about to be taken. Returns the table for
-        models._ops.set_fused_adam."""
+        models._wgrad.set_fused_adam."""
         if self.reducer is not None:
             raise ValueError("fused weight updates need the complete gradient on this GPU (no gradient exchange)")
         from models import _ops

@@ -303,7 +303,7 @@ def test_default_unet_step_vs_oracle(mode):
     """The benchmarked network (hidden 32, 5 scales, 645 M parameters) at the training crop size:
     restored images within 1e-4 relative and 0.01 dB PSNR of the float32 CPU path; loss and gradient
     norms within 1e-4 (SURVEY 8d 'parity check in the same run'). mode: the exact-f32 MFMA GEMMs, and the split-bf16
-    mode (three bf16 MFMA products per float32 product, models/_ops.py gemm_x3) held to the SAME bars."""
+    mode (three bf16 MFMA products per float32 product, models/_gemm.py gemm_x3) held to the SAME bars."""
     from models import _ops
     prev = _ops.set_compute_dtype(mode)
     try:
@@ -1438,14 +1438,14 @@ def test_two_models_in_one_process_keep_their_own_step_state():
         for bb in bbs:
             bb.zero_grad_flat()
         la, lb = loss_of(nets[0], 5), loss_of(nets[1], 5)
-        assert _ops.state_of(bbs[0])["uses"] == 2 and _ops.state_of(bbs[1])["uses"] == 2
+        assert _ops.state_of(bbs[0]).uses == 2 and _ops.state_of(bbs[1]).uses == 2
         la.backward()
         lb.backward()
         torch.cuda.synchronize()
         for bb, ref in zip(bbs, alone):
             assert relerr(bb.flat_grads, ref) < 2e-4
-            assert not _ops.state_of(bb)["parked"] and len(_ops.merged_weight_grads(bb)) > 4
-        assert _ops.state_of()["uses"] == 0                      # nothing leaked into the default state
+            assert not _ops.state_of(bb).parked and len(_ops.merged_weight_grads(bb)) > 4
+        assert _ops.state_of().uses == 0                      # nothing leaked into the default state
         # ... and a backbone may carry its own arithmetic mode: an exact-f32 model beside the bf16 one (process default
         # bf16), interleaved with it, gives the gradients it gives alone in an f32 process
         bbs[1].compute_dtype = "f32"

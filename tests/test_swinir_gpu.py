@@ -758,9 +758,9 @@ def test_conv_gemm_with_the_unpad_epilogue(B, H, W, Cin, Cout, act, with_res):
 def test_token_streaming_path_matches_the_tiled_path(cfg):
     """The bf16 SwinIR step on the token-streaming kernels (one launch for a block's four weight gradients, the layer's
     matrix in registers, LayerNorm forward / backward inside the GEMM epilogues, GELU' input recomputed) against the
-    same step on the tiled GEMMs + separate LayerNorm / cast kernels (`_ops.TOKEN_STREAMING = False`), same weights,
+    same step on the tiled GEMMs + separate LayerNorm / cast kernels (`_wgrad.TOKEN_STREAMING = False`), same weights,
     inputs and stochastic-depth masks: the two are different summation orders of the same bf16 products."""
-    from models import _ops
+    from models import _ops, _wgrad
     from models.swinir import SwinIR
     up = 2 if cfg.startswith("sr2") else 1
     depths = (3, 2)
@@ -782,7 +782,7 @@ def test_token_streaming_path_matches_the_tiled_path(cfg):
     prev = _ops.set_compute_dtype("bf16")
     try:
         for streaming in (True, False):
-            _ops.TOKEN_STREAMING = streaming
+            _wgrad.TOKEN_STREAMING = streaming
             with N_call_log() as log:
                 model.zero_grad_flat()
                 out = model(x, drop_masks=masks)
@@ -794,7 +794,7 @@ def test_token_streaming_path_matches_the_tiled_path(cfg):
             assert (new <= names) if streaming else not (new & names), sorted(names)
             outs[streaming] = (out.detach().clone(), model.flat_grads.clone())
     finally:
-        _ops.TOKEN_STREAMING = True
+        _wgrad.TOKEN_STREAMING = True
         _ops.set_compute_dtype(prev)
     assert relerr(outs[True][0], outs[False][0]) < 5e-3, relerr(outs[True][0], outs[False][0])
     base = model.flat_params.data_ptr()

@@ -1152,7 +1152,7 @@ def test_gemm_with_the_result_s_column_sums_in_the_epilogue(ops, M, N, K, brm):
     ops.gemm_nt16(A, B, M, N, K, ops.EPI_MUL_DGELU, out16=ref16, R1=R1, b_rmajor=bool(brm))
     base = torch.randn(N, generator=gen).cuda()
     want = base.clone()
-    ops.colsum16_into(want, ref16, leaf=False)
+    ops.colsum16_into(want, ref16)
     got16 = torch.empty_like(ref16)
     got = base.clone()
     ops.gemm_nt16(A, B, M, N, K, ops.EPI_MUL_DGELU, out16=got16, R1=R1, b_rmajor=bool(brm), colsum=got)
@@ -1406,6 +1406,7 @@ def test_deferred_folds_leave_the_gradients_bit_identical(ops, mode):
     bit-identical (the test above); whole passes differ by the float atomics of the split-K GEMMs upstream, run to run
     as much as mode to mode, hence a tolerance here."""
     import _native as N
+    from models import _wgrad
     from models.convolutional import ConvolutionalModel
     torch.manual_seed(0)
     m = ConvolutionalModel(in_channels=3, upsampling_rate=1, residual=True, inner_residual=True, num_conv_blocks=1,
@@ -1416,7 +1417,7 @@ def test_deferred_folds_leave_the_gradients_bit_identical(ops, mode):
     grads, folds = {}, {}
     try:
         for deferred in (False, True):
-            ops.DEFERRED_FOLDS = deferred
+            _wgrad.DEFERRED_FOLDS = deferred
             ops.set_weight_grad_merging(False, owner=m)      # (merged launches change the summation order of nothing here,
             m.zero_grad_flat()                               #  but keep the two passes independent of the parking logic)
             N.record_calls(True)
@@ -1425,7 +1426,7 @@ def test_deferred_folds_leave_the_gradients_bit_identical(ops, mode):
             folds[deferred] = sum(1 for name, _ in log if name == "sei_fold_many")
             grads[deferred] = m.flat_grads.clone()
     finally:
-        ops.DEFERRED_FOLDS = True
+        _wgrad.DEFERRED_FOLDS = True
         ops.set_weight_grad_merging(True, owner=m)
         ops.set_compute_dtype(prev)
     assert folds[False] == 0 and 1 <= folds[True] <= 2
@@ -1477,11 +1478,12 @@ def test_streamed_weight_gradients_of_the_shallow_levels(K1, K2):
 
 def test_streamed_weight_gradients_inside_a_backward_pass(ops):
     """The U-Net's backward pass in bf16 mode with the shallow levels' weight gradients collected into one job table per
-    block shape at the end of the pass (models/_ops._queue_dwstream) against the same pass on the tiled GEMMs
+    block shape at the end of the pass (models/_wgrad.py: queue_dwstream) against the same pass on the tiled GEMMs
     (SEI_NO_DWSTREAM): two model calls per step, so every job carries two pixel segments. Equal up to the float atomics'
     summation order and the bf16 roundings behind it: the bar is three times what two runs of the tiled path differ by
     (or 3e-3); the streamed path issues one launch where the tiled path issues one per weight."""
     import _native as N
+    from models import _wgrad
     from models.convolutional import ConvolutionalModel
     torch.manual_seed(0)
     m = ConvolutionalModel(in_channels=3, upsampling_rate=1, residual=True, inner_residual=True, num_conv_blocks=1,
@@ -1492,7 +1494,7 @@ def test_streamed_weight_gradients_inside_a_backward_pass(ops):
     grads, launches = {}, {}
     try:
         for streamed in (False, None, True):                  # (None: the tiled path a second time -- its own noise)
-            ops.DWSTREAM = bool(streamed)
+            _wgrad.DWSTREAM = bool(streamed)
             m.zero_grad_flat()
             N.record_calls(True)
             ((m(y) * ct).sum() + (m(y2) * ct2).sum()).backward()
@@ -1501,7 +1503,7 @@ def test_streamed_weight_gradients_inside_a_backward_pass(ops):
                                   sum(1 for name, _ in log if name.startswith("sei_gemm_bf16nt_dw2")))
             grads[streamed] = m.flat_grads.clone()
     finally:
-        ops.DWSTREAM = True
+        _wgrad.DWSTREAM = True
         ops.set_compute_dtype(prev)
     assert launches[False][0] == 0 and launches[True][0] == 1
     assert launches[True][1] <= launches[False][1] - 8, launches          # levels 0 and 1: 2 x (conv2, conv3) + 4 between levels
