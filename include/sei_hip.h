@@ -43,6 +43,7 @@ extern "C" {
  *                sei_ln_fwd, sei_ln_bwd (+ sei_ln_bwd_workspace), sei_gemm_f32, sei_colsum_f32, sei_sepmap2
  *   U-Net (bf16) sei_cast_bf16, sei_ln_fwd_bf16, sei_gemm_bf16nt
  *   optimizer    sei_adam_fused
+ *   baselines    sei_tv_prox (+ sei_tv_prox_work_floats)
  * INTERNAL -- everything else in this header: fused, schedule-specific (_ex, _ws, _dw2*, _plan, _eligible, _parts,
  * _count ...), SwinIR and measurement entry points that this build's own host layer (models/_ops.py, graphs.py, optim.py,
  * bench.py) calls. They are exported and documented here because that host layer sits above the C ABI, but they follow the
@@ -224,6 +225,31 @@ int sei_luma_sqerr(const float *a, const float *b, size_t npix, float *out1, flo
  * Deterministic: no atomics; an image's result does not depend on the batch it is in. */
 int sei_ssim_luma(const float *a, const float *b, int batch, int H, int W, float *out, float *work, void *stream);
 size_t sei_ssim_luma_work_floats(int batch, int H, int W);
+
+/* ---------------------------------------------------------------------------------------------
+ * Baselines of the evaluation driver (csrc/tv_kernels.hip; reference src/models/tv.py).
+ *
+ * sei_tv_prox: `iters` iterations of the primal-dual loop for prox_{ths TV}(z), isotropic TV with Neumann differences
+ * (deepinv v0.2.0's TVDenoiser as models/tv.py restates it: tau = 0.01, sigma = 1 / (8 tau), rho = 1.99), on `planes`
+ * independent planes:
+ *     x  = (x2 - tau nabla^T(u2) + tau z) / (1 + tau)
+ *     v  = u2 + sigma nabla(2 x - x2);   u = v / max(|v|_2 / ths, 1)      per pixel, over the two directions
+ *     x2 = x2 + rho (x - x2);   u2 = u2 + rho (u - u2)
+ * z and x2 are [planes][H][W]; u2 is [2][planes][H][W], the vertical differences then the horizontal ones. x2 and u2
+ * hold the incoming state and, on return, the state after `iters` iterations (the prox is x2). `work` holds
+ * sei_tv_prox_work_floats(planes, H, W) = 3 planes H W floats (0 = arguments refused): the launches alternate between
+ * the state and this copy. H, W >= 1 (tiled: no limit from LDS), iters >= 1, ths > 0; pointers 4-byte aligned.
+ * SEI_ERR_BAD_ARG on NULL / non-positive arguments and when z, x2, u2 or work overlap; SEI_ERR_TOO_LARGE only where
+ * the index arithmetic would overflow (more than 2^31 - 1 tiles, an extent above 2^30).
+ * Deterministic, no atomics, and exact under splitting: a call of a + b iterations leaves the bits that a call of a
+ * followed by a call of b leaves, whatever the schedule.
+ *   _ex: the schedule as per-call arguments: tile = 32 | 64 and k = 1 | 2 | 4 | 5 | 10 | 20 iterations per launch
+ *   (0 = the default of each); anything else is SEI_ERR_BAD_ARG. Same bits for every choice. */
+int sei_tv_prox(const float *z, float *x2, float *u2, int planes, int H, int W, float ths, int iters, float *work,
+                void *stream);
+int sei_tv_prox_ex(const float *z, float *x2, float *u2, int planes, int H, int W, float ths, int iters, int tile, int k,
+                   float *work, void *stream);
+size_t sei_tv_prox_work_floats(int planes, int H, int W);
 
 /* ---------------------------------------------------------------------------------------------
  * U-Net (src/models/convolutional.py), NHWC activations ("rows" = B*H*W pixels of C channels).

@@ -52,6 +52,8 @@ SIGNATURES = {
     "sei_mse_loss": [_P, _P, _Z, _F, _F, _P, _P, _P, _P],
     "sei_luma_sqerr": [_P, _P, _Z, _P, _P, _P],
     "sei_ssim_luma": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "sei_tv_prox": [_P, _P, _P, _I, _I, _I, _F, _I, _P, _P],
+    "sei_tv_prox_ex": [_P, _P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P],
     "sei_conv3x3_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sei_conv3x3_bwd_weight": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sei_conv3x3_bwd_weight_parts": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -174,6 +176,7 @@ TRANSPOSE_MAX_JOBS = 16
 SIZE_QUERIES = {
     "sei_proposed_draws_max_numel": [],
     "sei_ssim_luma_work_floats": [_I, _I, _I],
+    "sei_tv_prox_work_floats": [_I, _I, _I],
     "sei_dwconv7_bwd_weight_workspace": [_I, _I, _I, _I],
     "sei_dwconv7_bwd_weight_workspace_ex": [_I, _I, _I, _I, _I],
     "sei_ln_bwd_workspace": [_Z, _I],

@@ -7,8 +7,10 @@ the reference's (same keys), so checkpoints interchange.
 In scope: kind "Proposed" with architecture "Convolutional" (the in-tree U-Net) or "Transformer" (the
 reference's default: deepinv's SwinIR with the arguments at src/models/__init__.py:51-74, rebuilt in
 models/swinir.py from the published architecture -- deepinv is not part of the reference tree, parity
-unpinned), the trivial "Identity" and "InverseFilter", and the bicubic "Upsample" baseline. The other test-time
-baselines (DIP, PnP, BM3D, DiffPIR, DPS, TV) raise a clear error instead of silently running something else.
+unpinned), the trivial "Identity" and "InverseFilter", the bicubic "Upsample" baseline and the classical "TV" baseline
+(models/tv.py: proximal gradient on the sei_tv_prox kernel; it needs --tv_lambd, for which the reference has no default
+either). The other test-time baselines (DIP, PnP, BM3D, DiffPIR, DPS) need pretrained networks or a package that is not
+here; they raise a clear error instead of silently running something else.
 """
 from os import environ
 
@@ -19,8 +21,9 @@ from physics import _bands
 from physics._ops import SeparableResampleOp, apply_linear
 from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
+from .tv import TV
 
-_OUT_OF_SCOPE = ("DeepImagePrior", "PlugAndPlay", "BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS", "TV")
+_OUT_OF_SCOPE = ("DeepImagePrior", "PlugAndPlay", "BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS")
 
 
 class Identity(Module):
@@ -98,6 +101,8 @@ class Model(Module):
             self.model = InverseFilter(physics=physics)
         elif kind == "Upsample":                              # reference :137-138: by sr_factor whatever the task
             self.model = Upsample(factor=sr_factor)
+        elif kind == "TV":                                    # reference :131-132, 210-213: lambd and max_iter from test.py's flags
+            self.model = TV(physics=physics, **blueprint[TV.__name__])
         elif kind in _OUT_OF_SCOPE:
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
                                       "hot path this build implements")
@@ -150,6 +155,9 @@ def get_model(args, physics, device):
             "kind": args.model_kind,
         },
         ProposedModel.__name__: {"architecture": args.ProposedModel__architecture},
+        # (train.py's parser has neither flag; the reference passes a missing --tv_lambd on as None and dies in deepinv,
+        # TV raises NotImplementedError naming the flag)
+        TV.__name__: {"lambd": getattr(args, "tv_lambd", None), "max_iter": getattr(args, "tv_max_iter", None) or 300},
     }
     return Model(blueprint=blueprint, physics=physics, device=device,
                  data_parallel_devices=data_parallel_devices, **blueprint[Model.__name__])

@@ -10,10 +10,11 @@ quantise to 8 bits and clamp x, y, x_hat (reference :140-148), PSNR on the luma 
 the reference's summary lines. In scope: the Proposed model family and the Identity / InverseFilter / bicubic Upsample
 kinds, `--dataset div2k | single_image | synthetic` or a directory of PNG measurements, `--save_images`, `--save_psf`,
 `--indices`, `--print_all_metrics`, `--noise2inverse` (src/noise2inverse.py's sliced evaluation around the same
-backbone) and `--r2r`. `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
+backbone), `--r2r`, and the classical baseline `--model_kind TV --tv_lambd L [--tv_max_iter N]` (models/tv.py: proximal
+gradient on sei_tv_prox; without --tv_lambd it raises, the reference has no default either). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
 `SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. LPIPS always prints nan (pyiqa and its
-pretrained weights are not rebuilt). Out of scope and refused: DIP / PnP / BM3D / DiffPIR / DPS / TV baselines
-(SURVEY section 2).
+pretrained weights are not rebuilt). Out of scope and refused: DIP / PnP / BM3D / DiffPIR / DPS baselines (pretrained
+networks or the bm3d package).
 """
 import os
 import sys

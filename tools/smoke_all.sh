@@ -2,6 +2,7 @@
 # Runs every experiment / probe script under tools/ once, each under its own timeout, and records which still run against
 # the current ABI (VERDICT r4 housekeeping): `bash tools/smoke_all.sh <out dir under gpurun_out>` on the GPU box. A script
 # that times out after printing results is "ran (cut at the limit)"; one that raises is listed with its last line.
+# (exp_tv_prox.py prints one line per schedule as it goes, so a cut run still shows the schedules it reached.)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$1
 mkdir -p "$OUT"
