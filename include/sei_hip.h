@@ -632,7 +632,7 @@ int sei_mlp_fused_bwd(const float *go, const uint16_t *h2, const uint16_t *W2, c
  * (table ((2*8-1)^2, heads), index computed in-kernel) and the -100 mask of shifted windows are index arithmetic
  * inside the kernel. scale = head_dim^-0.5 (applied to q first, as the reference). head_dim 30 (SwinIR), 32, 16, 8.
  * sei_swin_attn_bwd: dqkv (every element written) and dtable (+=, float atomics) from dout; the probabilities are
- * recomputed from qkv. */
+ * recomputed from qkv. Both forms ADD into dtable, never overwrite it: the caller zeroes it once per step. */
 int sei_swin_attn_fwd(const float *qkv, const float *table, float *out, int B, int H, int W, int heads,
                       int head_dim, int shift, float scale, void *stream);
 int sei_swin_attn_bwd(const float *qkv, const float *table, const float *dout, float *dqkv, float *dtable,

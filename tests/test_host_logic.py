@@ -697,3 +697,42 @@ def test_alignment_predicate_of_the_float4_kernels():
     for k in (1, 2, 3, 5):
         assert not N.aligned(base[k:]) and not N.aligned(base, base[k:])
     assert N.aligned(base[2:], to=8) and not N.aligned(base[1:], to=8)
+
+
+@pytest.mark.parametrize("H,W", [(8, 8), (8, 24), (24, 8), (8, 16), (16, 8), (16, 16), (24, 16)])
+def test_oracle_shift_mask_is_the_published_calculate_mask(H, W):
+    """oracle/swinir_path.py::shift_mask against a literal transcription of SwinTransformerBlock.calculate_mask (the
+    published slice loops, windows cut out one by one) for every shift 1..7 and for extents with a single window row or
+    column, where slice(0, -8) is empty and there is no region 0 -- what a thin image gives after the forward's reflect
+    padding. The coordinate form the attention kernels use (csrc/swin_kernels.hip: win_token) is held to the same
+    tensor: a pair is masked, once, when its two region numbers differ."""
+    from oracle import swinir_path as sp
+    ws = 8
+    for shift in range(1, ws):
+        img_mask = torch.zeros((1, H, W, 1))
+        h_slices = (slice(0, -ws), slice(-ws, -shift), slice(-shift, None))
+        w_slices = (slice(0, -ws), slice(-ws, -shift), slice(-shift, None))
+        cnt = 0
+        for h in h_slices:
+            for w in w_slices:
+                img_mask[:, h, w, :] = cnt
+                cnt += 1
+        windows = [img_mask[0, y:y + ws, x:x + ws, 0].reshape(ws * ws) for y in range(0, H, ws) for x in range(0, W, ws)]
+        mask_windows = torch.stack(windows)
+        attn_mask = mask_windows.unsqueeze(1) - mask_windows.unsqueeze(2)
+        attn_mask = attn_mask.masked_fill(attn_mask != 0, float(-100.0)).masked_fill(attn_mask == 0, float(0.0))
+        got = sp.shift_mask(H, W, ws, shift)
+        assert got.shape == (H // ws * (W // ws), ws * ws, ws * ws) and torch.equal(got, attn_mask), (H, W, shift)
+        # the kernels' region arithmetic on shifted-frame coordinates (sy, sx)
+        region = torch.empty((H // ws) * (W // ws), ws * ws)
+        for win in range(region.shape[0]):
+            wy, wx = divmod(win, W // ws)
+            for i in range(ws * ws):
+                sy, sx = wy * ws + (i >> 3), wx * ws + (i & 7)
+                ry = 0 if sy < H - ws else (1 if sy < H - shift else 2)
+                rx = 0 if sx < W - ws else (1 if sx < W - shift else 2)
+                region[win, i] = 3 * ry + rx
+        coord = torch.where(region.unsqueeze(1) != region.unsqueeze(2), -100.0, 0.0)
+        assert torch.equal(coord, attn_mask), (H, W, shift)
+        if H == ws:
+            assert float(region.min()) >= 3                     # no region 0 .. 2: every window is a last-row window

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import swinir_path as sp
+from window_attention_ref import _attention_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -17,29 +18,6 @@ def relerr(a, b):
     a = a.detach().cpu().double().numpy()
     b = b.detach().cpu().double().numpy()
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def _attention_reference(qkv, table, B, H, W, heads, shift):
-    """WindowAttention on natural-order tokens by the reference's own steps: roll, window_partition, bias lookup,
-    mask, softmax, window_reverse, roll back (float64)."""
-    C = qkv.shape[1] // 3
-    x = qkv.view(B, H, W, 3 * C)
-    if shift:
-        x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
-    xw = sp.window_partition(x, 8).view(-1, 64, 3, heads, C // heads).permute(2, 0, 3, 1, 4)
-    q, k, v = xw[0] * (C // heads) ** -0.5, xw[1], xw[2]
-    attn = q @ k.transpose(-2, -1)
-    idx = sp.relative_position_index(8)
-    attn = attn + table[idx.view(-1)].view(64, 64, -1).permute(2, 0, 1).unsqueeze(0)
-    if shift:
-        mask = sp.shift_mask(H, W, 8, shift).to(attn.dtype)
-        nW = mask.shape[0]
-        attn = (attn.view(-1, nW, heads, 64, 64) + mask.unsqueeze(1).unsqueeze(0)).view(-1, heads, 64, 64)
-    out = (attn.softmax(-1) @ v).transpose(1, 2).reshape(-1, 8, 8, C)
-    out = sp.window_reverse(out, 8, H, W)
-    if shift:
-        out = torch.roll(out, shifts=(shift, shift), dims=(1, 2))
-    return out.reshape(B * H * W, C)
 
 
 @pytest.mark.parametrize("shift", [0, 4])
