@@ -251,6 +251,48 @@ int sei_tv_prox_ex(const float *z, float *x2, float *u2, int planes, int H, int 
                    float *work, void *stream);
 size_t sei_tv_prox_work_floats(int planes, int H, int W);
 
+/* The Deep Image Prior decoder (reference src/models/dip.py; deepinv v0.2.0's ConvDecoder as models/dip.py restates it),
+ * float32, ONE image, C = 32 channels (anything else: SEI_ERR_BAD_ARG). Activations are channels-last [H * W][32]; weights
+ * are in torch's layout, as they lie in the flat parameter bucket: w [32][32][3][3], head w [Cout][32]. A stage stores
+ * a_l = relu(conv3x3(nearest_upsample(BN_{l-1}(a_{l-1}))) + bias); BN_{l-1} reaches it as ss_prev = {scale[32], shift[32]}
+ * applied on load (NULL: the identity, the first stage reading z), the nearest index is torch's
+ * min(floor(dst * (float(in) / float(out))), in - 1), and the zero padding is zero AFTER the affine. Neither the
+ * upsampled nor the normalised tensor is stored.
+ *   sei_dip_stage_fwd        a_out [Hout * Wout][32] and stats = {mean[32], rstd[32], scale[32], shift[32]} of ITS batch
+ *                            norm (training mode: biased variance over the Hout * Wout pixels, eps; scale = gamma rstd,
+ *                            shift = beta - mean scale; stats + 64 is the next stage's ss_prev). Per-workgroup (sum, M2)
+ *                            partials, combined pairwise in double: no cancellation.
+ *   sei_dip_head_fwd         x_hat [Cout][H * W] (NCHW) = w BN(a) + bias, 1 <= Cout <= 8; ss = that BN's {scale, shift}.
+ *   sei_dip_head_bwd         from g_x [Cout][H * W]: g_bn [H * W][32] (gradient at the BN's output), g_w [Cout][32], g_bias.
+ *   sei_dip_stage_bwd_bn     g [H * W][32] holds the gradient at the BN's output and, on return, the gradient at the
+ *                            convolution's output: relu_mask scale (g - mean(g) - x_norm mean(g x_norm)); g_gamma[32] =
+ *                            sum g x_norm, g_beta[32] = sum g, with g_beta == g_gamma + 32 (their place in the bucket).
+ *   sei_dip_stage_bwd_data   g_prev [Hin * Win][32]: the gradient at BN_{l-1}'s output -- the transposed convolution
+ *                            gathered over the block of destination pixels that each source pixel feeds (no scatter).
+ *   sei_dip_stage_bwd_weight g_w [32][32][3][3] and g_bias[32]; reads a_prev through the forward's load path.
+ *   sei_dip_adam             torch.optim.Adam's update (sei_adam_fused's arithmetic, gradient scale 1) with the step's six
+ *                            scalars read from the DEVICE array that sei_adam_scalars_to_device fills: a captured launch
+ *                            serves every step.
+ * `work` holds sei_dip_work_floats(H, W, C, Cout) floats for the OUTPUT extent of the call (0 = arguments refused); a
+ * decoder takes the maximum over its stages. Extents 1 .. 16384 (beyond: SEI_ERR_TOO_LARGE); activation pointers 16-byte
+ * aligned, everything else 4-byte. No atomics, fixed summation order: the same bits on every run. */
+size_t sei_dip_work_floats(int H, int W, int C, int Cout);
+int sei_dip_stage_fwd(const float *a_prev, const float *ss_prev, const float *w, const float *bias, const float *gamma,
+                      const float *beta, float *a_out, float *stats, int Hin, int Win, int Hout, int Wout, int C, float eps,
+                      float *work, void *stream);
+int sei_dip_head_fwd(const float *a, const float *ss, const float *w, const float *bias, float *x_hat, int H, int W, int C,
+                     int Cout, void *stream);
+int sei_dip_head_bwd(const float *g_x, const float *a, const float *ss, const float *w, float *g_bn, float *g_w,
+                     float *g_bias, int H, int W, int C, int Cout, float *work, void *stream);
+int sei_dip_stage_bwd_bn(float *g, const float *a, const float *stats, float *g_gamma, float *g_beta, int H, int W, int C,
+                         float *work, void *stream);
+int sei_dip_stage_bwd_data(const float *g_conv, const float *w, float *g_prev, int Hin, int Win, int Hout, int Wout, int C,
+                           void *stream);
+int sei_dip_stage_bwd_weight(const float *g_conv, const float *a_prev, const float *ss_prev, float *g_w, float *g_bias,
+                             int Hin, int Win, int Hout, int Wout, int C, float *work, void *stream);
+int sei_dip_adam(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, const float *hyper6,
+                 void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * U-Net (src/models/convolutional.py), NHWC activations ("rows" = B*H*W pixels of C channels).
  * Parameter-gradient outputs (gw, gb, ggamma, gbeta, colsum `out`) are ACCUMULATED into with float

@@ -54,6 +54,13 @@ SIGNATURES = {
     "sei_ssim_luma": [_P, _P, _I, _I, _I, _P, _P, _P],
     "sei_tv_prox": [_P, _P, _P, _I, _I, _I, _F, _I, _P, _P],
     "sei_tv_prox_ex": [_P, _P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P],
+    "sei_dip_stage_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P],
+    "sei_dip_head_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "sei_dip_head_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "sei_dip_stage_bwd_bn": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "sei_dip_stage_bwd_data": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sei_dip_stage_bwd_weight": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "sei_dip_adam": [_P, _P, _P, _P, _Z, _P, _P],
     "sei_conv3x3_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sei_conv3x3_bwd_weight": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sei_conv3x3_bwd_weight_parts": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -177,6 +184,7 @@ SIZE_QUERIES = {
     "sei_proposed_draws_max_numel": [],
     "sei_ssim_luma_work_floats": [_I, _I, _I],
     "sei_tv_prox_work_floats": [_I, _I, _I],
+    "sei_dip_work_floats": [_I, _I, _I, _I],
     "sei_dwconv7_bwd_weight_workspace": [_I, _I, _I, _I],
     "sei_dwconv7_bwd_weight_workspace_ex": [_I, _I, _I, _I, _I],
     "sei_ln_bwd_workspace": [_Z, _I],

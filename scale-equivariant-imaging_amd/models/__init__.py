@@ -7,10 +7,13 @@ the reference's (same keys), so checkpoints interchange.
 In scope: kind "Proposed" with architecture "Convolutional" (the in-tree U-Net) or "Transformer" (the
 reference's default: deepinv's SwinIR with the arguments at src/models/__init__.py:51-74, rebuilt in
 models/swinir.py from the published architecture -- deepinv is not part of the reference tree, parity
-unpinned), the trivial "Identity" and "InverseFilter", the bicubic "Upsample" baseline and the classical "TV" baseline
+unpinned), the trivial "Identity" and "InverseFilter", the bicubic "Upsample" baseline, the classical "TV" baseline
 (models/tv.py: proximal gradient on the sei_tv_prox kernel; it needs --tv_lambd, for which the reference has no default
-either). The other test-time baselines (DIP, PnP, BM3D, DiffPIR, DPS) need pretrained networks or a package that is not
-here; they raise a clear error instead of silently running something else.
+either) and "DeepImagePrior" (models/dip.py: deepinv's untrained ConvDecoder restated, fitted to each measurement by Adam on
+the fused sei_dip_* kernels; parity with deepinv unpinned, the float64 restatement in tests/test_dip_baseline_gpu.py is the
+pinned truth; --dip_iterations, with the reference's defaults for deblurring and sr). The other test-time baselines (PnP,
+BM3D, DiffPIR, DPS) need pretrained networks or a package that is not here; they raise a clear error instead of silently
+running something else.
 """
 from os import environ
 
@@ -21,9 +24,10 @@ from physics import _bands
 from physics._ops import SeparableResampleOp, apply_linear
 from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
+from .dip import DeepImagePrior
 from .tv import TV
 
-_OUT_OF_SCOPE = ("DeepImagePrior", "PlugAndPlay", "BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS")
+_OUT_OF_SCOPE = ("PlugAndPlay", "BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS")
 
 
 class Identity(Module):
@@ -103,6 +107,8 @@ class Model(Module):
             self.model = Upsample(factor=sr_factor)
         elif kind == "TV":                                    # reference :131-132, 210-213: lambd and max_iter from test.py's flags
             self.model = TV(physics=physics, **blueprint[TV.__name__])
+        elif kind == "DeepImagePrior":                        # reference :109-114: sr_factor whatever the task
+            self.model = DeepImagePrior(physics=physics, sr_factor=sr_factor, **blueprint[DeepImagePrior.__name__])
         elif kind in _OUT_OF_SCOPE:
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
                                       "hot path this build implements")
@@ -136,6 +142,20 @@ class Model(Module):
         self.get_backbone().load_state_dict(state_dict)
 
 
+def _dip_iterations(args):
+    """--dip_iterations, else the reference's defaults (:194-205): 4000 for deblurring with a Gaussian kernel, 1000 for
+    other deblurring and for sr. For any other task the reference leaves the name unbound."""
+    given = getattr(args, "dip_iterations", None)
+    if given is not None:
+        return given
+    if args.task == "deblurring":
+        return 4000 if "Gaussian" in (args.kernel or "") else 1000
+    if args.task == "sr":
+        return 1000
+    raise ValueError(f"model kind 'DeepImagePrior' has no default iteration count for --task {args.task}: "
+                     "give --dip_iterations")
+
+
 def get_model(args, physics, device):
     data_parallel_devices = (args.data_parallel_devices.split(",")
                              if args.data_parallel_devices is not None else None)
@@ -157,6 +177,7 @@ def get_model(args, physics, device):
         ProposedModel.__name__: {"architecture": args.ProposedModel__architecture},
         # (train.py's parser has neither flag; the reference passes a missing --tv_lambd on as None and dies in deepinv,
         # TV raises NotImplementedError naming the flag)
+        DeepImagePrior.__name__: {"iterations": _dip_iterations(args) if args.model_kind == "DeepImagePrior" else None},
         TV.__name__: {"lambd": getattr(args, "tv_lambd", None), "max_iter": getattr(args, "tv_max_iter", None) or 300},
     }
     return Model(blueprint=blueprint, physics=physics, device=device,

@@ -11,9 +11,11 @@ the reference's summary lines. In scope: the Proposed model family and the Ident
 kinds, `--dataset div2k | single_image | synthetic` or a directory of PNG measurements, `--save_images`, `--save_psf`,
 `--indices`, `--print_all_metrics`, `--noise2inverse` (src/noise2inverse.py's sliced evaluation around the same
 backbone), `--r2r`, and the classical baseline `--model_kind TV --tv_lambd L [--tv_max_iter N]` (models/tv.py: proximal
-gradient on sei_tv_prox; without --tv_lambd it raises, the reference has no default either). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
+gradient on sei_tv_prox; without --tv_lambd it raises, the reference has no default either) and `--model_kind DeepImagePrior
+[--dip_iterations N]` (models/dip.py: an untrained decoder fitted to every measurement by Adam on the sei_dip_* kernels; its
+forward needs no autograd, so the reference's `dip` switch around no_grad has nothing to do here). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
 `SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. LPIPS always prints nan (pyiqa and its
-pretrained weights are not rebuilt). Out of scope and refused: DIP / PnP / BM3D / DiffPIR / DPS baselines (pretrained
+pretrained weights are not rebuilt). Out of scope and refused: PnP / BM3D / DiffPIR / DPS baselines (pretrained
 networks or the bm3d package).
 """
 import os
@@ -79,8 +81,6 @@ def main(argv=None):
     torch.manual_seed(0)
     np.random.seed(0)
     args = build_parser().parse_args(argv)
-    if args.model_kind == "dip":
-        raise NotImplementedError("DIP evaluation is outside the hot path of this build")
     from models import _ops as model_ops
     model_ops.set_compute_dtype(args.compute_dtype)
 
