@@ -4,12 +4,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned short f2bf(float v) {
-    const __bf16 b = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
-
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float *__restrict__ x, unsigned short *__restrict__ y,
                                                         size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -17,19 +11,19 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float *__restrict_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4 *>(x)[i];
         ushort4 o;
-        o.x = f2bf(v.x); o.y = f2bf(v.y); o.z = f2bf(v.z); o.w = f2bf(v.w);
+        o.x = sei_f2bf(v.x); o.y = sei_f2bf(v.y); o.z = sei_f2bf(v.z); o.w = sei_f2bf(v.w);
         reinterpret_cast<ushort4 *>(y)[i] = o;
     }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = f2bf(x[i]);
+    for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = sei_f2bf(x[i]);
 }
 
-__device__ __forceinline__ unsigned short to_bf(float v) { return f2bf(v); }
+__device__ __forceinline__ unsigned short to_bf(float v) { return sei_f2bf(v); }
 __device__ __forceinline__ unsigned short to_bf(unsigned short v) { return v; }
 
 // x (R, C) f32 or bf16 -> x16 (R, C) bf16 (optional) and xt16 (C, ldt) bf16 (optional; columns R..ldt-1
 // are zero-filled so that the transposed matrix can be a K-padded GEMM operand). 64x64 tiles through LDS.
 __device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(unsigned short v) { return bf2f(v); }
+__device__ __forceinline__ float to_f(unsigned short v) { return sei_bf2f(v); }
 
 // colsum (optional): colsum[c] += sum_r x[r][c] in float32 from the UN-rounded input (bias gradients),
 // one atomic per column per 64-row tile.
@@ -124,15 +118,8 @@ __global__ __launch_bounds__(256) void cast_colsum_kernel(const float *__restric
     }
 }
 
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // LayerNorm over C with a bf16 output (and f32 mean / rstd for the backward). One workgroup row-group
-// layout as in unet_kernels.hip: G lanes per row for C <= 512, one workgroup per row above.
+// layout as in ln_kernels.hip: G lanes per row for C <= 512, one workgroup per row above.
 template <int G>
 __global__ __launch_bounds__(256) void ln_fwd_bf16_group_kernel(const float *__restrict__ x,
                                                                 const float *__restrict__ gamma,
@@ -153,7 +140,7 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_group_kernel(const float *__r
             v[e] = c < C ? xr[c] : 0.f;
             s += v[e];
         }
-        const float mu = group_sum<G>(s) * invC;
+        const float mu = sei_group_sum<G>(s) * invC;
         float q = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -161,12 +148,12 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_group_kernel(const float *__r
             const float d = c < C ? v[e] - mu : 0.f;
             q = fmaf(d, d, q);
         }
-        const float rs = 1.0f / sqrtf(group_sum<G>(q) * invC + eps);
+        const float rs = 1.0f / sqrtf(sei_group_sum<G>(q) * invC + eps);
         unsigned short *yr = y + row * C;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = lg + e * G;
-            if (c < C) yr[c] = f2bf(fmaf((v[e] - mu) * rs, gamma[c], beta[c]));
+            if (c < C) yr[c] = sei_f2bf(fmaf((v[e] - mu) * rs, gamma[c], beta[c]));
         }
         if (lg == 0) {
             mean[row] = mu;
@@ -178,8 +165,8 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_group_kernel(const float *__r
 // four normalised values of one quad: 8 bytes of bf16 or 16 bytes of float32 (sei_ln_fwd's fast path, round 5)
 __device__ __forceinline__ void ln_store4(unsigned short *p, float a, float b, float c, float d) {
     uint2 w;
-    w.x = (unsigned)f2bf(a) | ((unsigned)f2bf(b) << 16);
-    w.y = (unsigned)f2bf(c) | ((unsigned)f2bf(d) << 16);
+    w.x = sei_pack2_bf16(a, b);
+    w.y = sei_pack2_bf16(c, d);
     *reinterpret_cast<uint2 *>(p) = w;
 }
 __device__ __forceinline__ void ln_store4(float *p, float a, float b, float c, float d) {
@@ -213,14 +200,14 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_quad_kernel(const float *__re
             v[e] = *reinterpret_cast<const float4 *>(x + row * C + 4 * (lg + e * L));
             s += (v[e].x + v[e].y) + (v[e].z + v[e].w);
         }
-        const float mu = group_sum<L>(s) * invC;
+        const float mu = sei_group_sum<L>(s) * invC;
         float q = 0.f;
 #pragma unroll
         for (int e = 0; e < NV; ++e) {
             const float dx = v[e].x - mu, dy = v[e].y - mu, dz = v[e].z - mu, dw = v[e].w - mu;
             q = fmaf(dx, dx, q); q = fmaf(dy, dy, q); q = fmaf(dz, dz, q); q = fmaf(dw, dw, q);
         }
-        const float rs = 1.0f / sqrtf(group_sum<L>(q) * invC + eps);
+        const float rs = 1.0f / sqrtf(sei_group_sum<L>(q) * invC + eps);
 #pragma unroll
         for (int e = 0; e < NV; ++e) {
             ln_store4(y + row * C + 4 * (lg + e * L), fmaf((v[e].x - mu) * rs, gam[e].x, bet[e].x),
@@ -272,7 +259,7 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_wide_kernel(const float *__re
 #pragma unroll
         for (int e = 0; e < 32; ++e) {
             const int c = threadIdx.x + e * 256;
-            if (c < C) yr[c] = f2bf(fmaf((v[e] - mu) * rs, gamma[c], beta[c]));
+            if (c < C) yr[c] = sei_f2bf(fmaf((v[e] - mu) * rs, gamma[c], beta[c]));
         }
         if (threadIdx.x == 0) {
             mean[row] = mu;
@@ -370,7 +357,7 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const unsigned short *
     const int c = blockIdx.y * cw + cl;
     float s = 0.f;
     if (c < N && rsub < rsubs)
-        for (size_t r = r0 + rsub; r < r1; r += rsubs) s += bf2f(X[r * N + c]);
+        for (size_t r = r0 + rsub; r < r1; r += rsubs) s += sei_bf2f(X[r * N + c]);
     if (rsub < rsubs) red[rsub * cw + cl] = s;
     __syncthreads();
     if (rsub == 0 && c < N) {
@@ -572,8 +559,8 @@ extern "C" int sei_cast_transpose_bf16(const void *x, int x_is_bf16, uint16_t *x
     return sei_launch_status();
 }
 
-// sei_ln_fwd's 16-byte-lane path (unet_kernels.hip calls it first): the kernels above with a float32 result. Returns -1 for
-// shapes they do not take (the scalar-lane kernels of unet_kernels.hip then run). The Downsample LayerNorms of the U-Net
+// sei_ln_fwd's 16-byte-lane path (ln_kernels.hip calls it first): the kernels above with a float32 result. Returns -1 for
+// shapes they do not take (the scalar-lane kernels of ln_kernels.hip then run). The Downsample LayerNorms of the U-Net
 // (147456 x 32 ... 2304 x 2048 per step) ran at 1.6-2.1 TB/s on 4-byte lanes.
 __attribute__((visibility("hidden"))) int sei_ln_fwd_f32_lanes16(const float *x, const float *gamma, const float *beta, float *y,
                                                                  float *mean, float *rstd, size_t rows, int C, float eps,

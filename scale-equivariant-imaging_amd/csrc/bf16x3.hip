@@ -9,12 +9,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned short x3_f2bf(float v) {
-    const __bf16 b = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float x3_bf2f(unsigned short u) { return __builtin_bit_cast(float, (unsigned)u << 16); }
-
 // planes[i] = bf16(x[i]); planes[n + i] = bf16(x[i] - float(planes[i]))
 __global__ __launch_bounds__(256) void split_bf16x2_kernel(const float *__restrict__ x, unsigned short *__restrict__ hi,
                                                            unsigned short *__restrict__ lo, size_t n) {
@@ -22,16 +16,16 @@ __global__ __launch_bounds__(256) void split_bf16x2_kernel(const float *__restri
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4 *>(x)[i];
         ushort4 h, l;
-        h.x = x3_f2bf(v.x); h.y = x3_f2bf(v.y); h.z = x3_f2bf(v.z); h.w = x3_f2bf(v.w);
-        l.x = x3_f2bf(v.x - x3_bf2f(h.x)); l.y = x3_f2bf(v.y - x3_bf2f(h.y));
-        l.z = x3_f2bf(v.z - x3_bf2f(h.z)); l.w = x3_f2bf(v.w - x3_bf2f(h.w));
+        h.x = sei_f2bf(v.x); h.y = sei_f2bf(v.y); h.z = sei_f2bf(v.z); h.w = sei_f2bf(v.w);
+        l.x = sei_f2bf(v.x - sei_bf2f(h.x)); l.y = sei_f2bf(v.y - sei_bf2f(h.y));
+        l.z = sei_f2bf(v.z - sei_bf2f(h.z)); l.w = sei_f2bf(v.w - sei_bf2f(h.w));
         reinterpret_cast<ushort4 *>(hi)[i] = h;
         reinterpret_cast<ushort4 *>(lo)[i] = l;
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned short h = x3_f2bf(x[i]);
+        const unsigned short h = sei_f2bf(x[i]);
         hi[i] = h;
-        lo[i] = x3_f2bf(x[i] - x3_bf2f(h));
+        lo[i] = sei_f2bf(x[i] - sei_bf2f(h));
     }
 }
 
@@ -45,9 +39,9 @@ __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float *__restri
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4 *>(x)[i];
         ushort4 h, l;
-        h.x = x3_f2bf(v.x); h.y = x3_f2bf(v.y); h.z = x3_f2bf(v.z); h.w = x3_f2bf(v.w);
-        l.x = x3_f2bf(v.x - x3_bf2f(h.x)); l.y = x3_f2bf(v.y - x3_bf2f(h.y));
-        l.z = x3_f2bf(v.z - x3_bf2f(h.z)); l.w = x3_f2bf(v.w - x3_bf2f(h.w));
+        h.x = sei_f2bf(v.x); h.y = sei_f2bf(v.y); h.z = sei_f2bf(v.z); h.w = sei_f2bf(v.w);
+        l.x = sei_f2bf(v.x - sei_bf2f(h.x)); l.y = sei_f2bf(v.y - sei_bf2f(h.y));
+        l.z = sei_f2bf(v.z - sei_bf2f(h.z)); l.w = sei_f2bf(v.w - sei_bf2f(h.w));
         reinterpret_cast<ushort4 *>(p0)[i] = h;
         reinterpret_cast<ushort4 *>(p1)[i] = pattern ? l : h;
         reinterpret_cast<ushort4 *>(p2)[i] = pattern ? h : l;
@@ -77,10 +71,7 @@ __global__ __launch_bounds__(256) void mul_dgelu_f32_kernel(float *__restrict__ 
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) d[i] *= sei_dgelu(h[i]);
 }
 
-inline unsigned x3_grid(size_t n) {
-    size_t grid = sei_ceil_div(n / 4 + 1, 256);
-    return (unsigned)(grid > 4096 ? 4096 : grid);
-}
+inline unsigned x3_grid(size_t n) { return sei_capped_grid(n / 4 + 1, 256, 4096); }
 
 }  // namespace
 

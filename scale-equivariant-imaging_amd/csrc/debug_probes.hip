@@ -2,7 +2,6 @@
 #include "sei_common.h"
 
 namespace {
-typedef short v4s __attribute__((ext_vector_type(4)));
 
 // LDS image: 64 rows x 128 columns of 16-bit values, plain row-major (256-byte rows, no swizzle).
 // Each 16-lane group g reads the 4x16 block with top-left (r0 + 4*g, c0): lane 4q+p supplies the

@@ -27,11 +27,8 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
-typedef short v4s __attribute__((ext_vector_type(4)));
 
 // 16-B chunk swizzle of a [64 rows][64 columns] bf16 image (128-B rows): as token_gemm.hip / gemm_bf16pq.h
 __device__ __forceinline__ int ds_swz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }

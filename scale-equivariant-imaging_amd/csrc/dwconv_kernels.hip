@@ -21,13 +21,6 @@ namespace {
 constexpr int DW_THREADS = 256;
 constexpr int DW_SEG = 16;           // generic kernel: output columns per worker segment unless the caller says
 
-inline unsigned capped_grid(size_t work_items, int per_block, unsigned cap) {
-    size_t g = sei_ceil_div(work_items, (size_t)per_block);
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
 // =================================================================================================
 // generic: one thread = one channel; a "worker" (Cc consecutive threads) walks a segment of one output row
 // with a 7x7 register window that slides by one column per step (7 new loads + 49 FMA per output).
@@ -475,7 +468,7 @@ inline DwWgradPlan dw_wgrad_plan(int B, int H, int W, int C, int seg) {
         p.nseg = (int)sei_ceil_div(W, p.seg);
         p.total = (size_t)B * H * p.nseg;
         p.gy = (unsigned)sei_ceil_div(C, p.Cc);
-        p.gx = capped_grid(p.total, workers * 2, 65535);
+        p.gx = sei_capped_grid(p.total, workers * 2, 65535);
         const unsigned max_gx = 4096 / p.gy > 0 ? 4096 / p.gy : 1;
         if (p.gx > max_gx) p.gx = max_gx;
         p.nparts = p.gx;
@@ -530,7 +523,7 @@ extern "C" int sei_dwconv7_fwd_ex(const float *x, const float *w, const float *b
             const int nseg = (int)sei_ceil_div(W, gseg);
             const size_t total = (size_t)B * H * nseg;
             SEI_REQUIRE(total < (size_t)1 << 31);
-            dim3 grid(capped_grid(total, workers, 65535), (unsigned)sei_ceil_div(C, Cc));
+            dim3 grid(sei_capped_grid(total, workers, 65535), (unsigned)sei_ceil_div(C, Cc));
             hipLaunchKernelGGL(dwconv7_kernel<false>, grid, dim3(DW_THREADS), 0, s, x, w, bias, res, res_scale, y, nof,
                                nom, B, H, W, C, flip ? 1 : 0, Cc, nseg, (int)total, gseg);
         }

@@ -34,11 +34,6 @@ constexpr int DP_WBYTES = DP_CC * 49 * 4;       // 6272 B of weights per group
 constexpr int DP_WPIECES = 7;                   // ... in 7 pieces of 1 KiB (the tail fed from the zero chunk)
 constexpr int DP_WBUF = DP_WPIECES * 1024;
 
-__device__ __forceinline__ unsigned short dp_f2bf(float v) {
-    const __bf16 b = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, b);
-}
-
 // Sum of v[p] over the 32 lanes of a half wave, for 16 values at once: after the five exchange steps lane cl holds
 // the total of value (cl >> 1). 16 exchanges + 16 adds (a butterfly per value would be 80 + 80).
 __device__ __forceinline__ float dp_transpose_sum16(const float (&v)[16], int cl) {
@@ -66,7 +61,8 @@ __device__ __forceinline__ float dp_transpose_sum16(const float (&v)[16], int cl
 }
 
 // s_waitcnt vmcnt(n) for a wave-uniform n in 0..16: wait until all but the wave's n youngest vector-memory operations
-// are done (the counter runs in issue order over loads, stores and LDS-DMA alike).
+// are done (the counter runs in issue order over loads, stores and LDS-DMA alike). Private: sei_wait_vmcnt<N> takes a
+// compile-time count, this one a run-time count.
 __device__ __forceinline__ void dp_wait_vmcnt(int n) {
     switch (n) {
 #define SEI_DP_W(N_) case N_: asm volatile("s_waitcnt vmcnt(" #N_ ")" ::: "memory"); break;
@@ -312,7 +308,7 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dwconv7_pipe_kernel(
                         for (int g = 0; g < LNG; ++g) {
                             const float o = fmaf((av[g][jl] - mu[jl]) * rs, gam[g], bet[g]);
                             const size_t e = hbase + (size_t)jl * C + g * DP_CC;
-                            if (OUT16) reinterpret_cast<unsigned short *>(h2)[e] = dp_f2bf(o);
+                            if (OUT16) reinterpret_cast<unsigned short *>(h2)[e] = sei_f2bf(o);
                             else reinterpret_cast<float *>(h2)[e] = o;
                         }
                     }

@@ -18,9 +18,6 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int BK = 32;
 constexpr int KBLK = BK / 8;
 

@@ -27,13 +27,8 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
-
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 64;
 constexpr int ROW_BYTES = 128;
@@ -99,23 +94,17 @@ struct NtArgs {
     int force_splitk;
 };
 
-typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 nt_load4(const float *p) {
-    const nt_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f32x4 *>(p));
+    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void nt_store4(float *p, const float4 v) {
-    nt_f32x4 t;
+    f32x4 t;
     t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-    __builtin_nontemporal_store(t, reinterpret_cast<nt_f32x4 *>(p));
+    __builtin_nontemporal_store(t, reinterpret_cast<f32x4 *>(p));
 }
 
 // (LDS-DMA pieces go out through sei_common.h's dma16_base / dma16_lane: inline asm, see there)
-
-__device__ __forceinline__ unsigned short f2bf(float v) {
-    const __bf16 b = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, b);
-}
 
 // ---- operand stored K-contiguous: element (o, k) at G[o*ld + k]; LDS image [o][128 B], chunk swizzle (r>>1)&7
 // One 1-KiB wave-instruction ("piece") of a ROWS-row tile: piece q covers rows 8q .. 8q+7.
@@ -175,19 +164,6 @@ __device__ __forceinline__ bf16x8 frag_rmajor(const char *tile, int s, int lane,
     const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(addr(row + 4));
     const v8s both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, both);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {          // counted wait: at most N LDS-DMA loads still in flight
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else static_assert(N < 0, "add the immediate");
 }
 
 // the row-patch epilogue (ROWEPI == 4) needs one wave row of the tile (32 TM rows x BN floats) inside the operand stages
@@ -449,8 +425,8 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
         int slot = 0;
         for (int t = 0; t < nt; ++t) {
             // tile t must have landed: everything issued after it may still be in flight
-            if (t + NSTAGE - 2 < nt) wait_vmcnt<(NSTAGE - 2) * PER>();
-            else wait_vmcnt<0>();
+            if (t + NSTAGE - 2 < nt) sei_wait_vmcnt<(NSTAGE - 2) * PER>();
+            else sei_wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();          // every wave's share of tile t is in LDS; slot t-1 is free
             const int tn = t + NSTAGE - 1;
             if (tn < nt) {
@@ -461,7 +437,7 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
             compute(smem + slot * STAGE);
             if (++slot == NSTAGE) slot = 0;
         }
-        wait_vmcnt<0>();
+        sei_wait_vmcnt<0>();
     }
 
     // ---- epilogue: optimizer step on the finished gradient tile (never split over K) ---------------------------
@@ -490,8 +466,8 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
                 if (row >= M || col >= N) continue;                  // N % 8 == 0: a quad is all in or all out
                 const float4 v = *reinterpret_cast<const float4 *>(patch + r * 128 + 4 * c4);
                 uint2 w;
-                w.x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
-                w.y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
+                w.x = sei_pack2_bf16(v.x, v.y);
+                w.y = sei_pack2_bf16(v.z, v.w);
                 *reinterpret_cast<uint2 *>(g.D16 + (size_t)row * N + col) = w;
             }
         }
@@ -543,12 +519,11 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
                 nt_store4(g.adam_p + off[k], o);
                 if (g.adam_p16) {
                     uint2 w;
-                    w.x = (unsigned)f2bf(o.x) | ((unsigned)f2bf(o.y) << 16);
-                    w.y = (unsigned)f2bf(o.z) | ((unsigned)f2bf(o.w) << 16);
-                    typedef unsigned nt_u32x2 __attribute__((ext_vector_type(2)));
-                    nt_u32x2 t;
+                    w.x = sei_pack2_bf16(o.x, o.y);
+                    w.y = sei_pack2_bf16(o.z, o.w);
+                    u32x2 t;
                     t.x = w.x; t.y = w.y;
-                    __builtin_nontemporal_store(t, reinterpret_cast<nt_u32x2 *>(g.adam_p16 + off[k]));
+                    __builtin_nontemporal_store(t, reinterpret_cast<u32x2 *>(g.adam_p16 + off[k]));
                 }
             }
           }
@@ -651,15 +626,15 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
                     }
                     if (epi == SEI_EPI_BIAS_GELU) {
                         uint2 w;
-                        w.x = (unsigned)f2bf(sei_gelu_bf16out(o.x)) | ((unsigned)f2bf(sei_gelu_bf16out(o.y)) << 16);
-                        w.y = (unsigned)f2bf(sei_gelu_bf16out(o.z)) | ((unsigned)f2bf(sei_gelu_bf16out(o.w)) << 16);
+                        w.x = (unsigned)sei_f2bf(sei_gelu_bf16out(o.x)) | ((unsigned)sei_f2bf(sei_gelu_bf16out(o.y)) << 16);
+                        w.y = (unsigned)sei_f2bf(sei_gelu_bf16out(o.z)) | ((unsigned)sei_f2bf(sei_gelu_bf16out(o.w)) << 16);
                         *reinterpret_cast<uint2 *>(g.D2_16 + off[u]) = w;
                     }
                     if (D32p) *reinterpret_cast<float4 *>(D32p + off[u]) = o;
                     if (g.D16) {
                         uint2 w;
-                        w.x = (unsigned)f2bf(o.x) | ((unsigned)f2bf(o.y) << 16);
-                        w.y = (unsigned)f2bf(o.z) | ((unsigned)f2bf(o.w) << 16);
+                        w.x = sei_pack2_bf16(o.x, o.y);
+                        w.y = sei_pack2_bf16(o.z, o.w);
                         *reinterpret_cast<uint2 *>(g.D16 + off[u]) = w;
                     }
                 }
@@ -706,9 +681,9 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
                     v *= (g.D16 && !D32p) ? sei_dgelu_bf16out(a1[i][j][r]) : sei_dgelu(a1[i][j][r]);
                 else if (epi == SEI_EPI_BIAS_SCALE_RES) v = fmaf(v, g.R1[row], a1[i][j][r]);
                 else v += a1[i][j][r] + a2[i][j][r];
-                if (epi == SEI_EPI_BIAS_GELU) g.D2_16[o] = f2bf(sei_gelu_bf16out(v));
+                if (epi == SEI_EPI_BIAS_GELU) g.D2_16[o] = sei_f2bf(sei_gelu_bf16out(v));
                 if (D32p) D32p[o] = v;
-                if (g.D16) g.D16[o] = f2bf(v);
+                if (g.D16) g.D16[o] = sei_f2bf(v);
             }
         }
     }

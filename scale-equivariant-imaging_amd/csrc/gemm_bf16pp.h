@@ -301,7 +301,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16pp_kernel(NtArgs g) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int dr = (r & 3) + 8 * (r >> 2);
-                    if (col_ok && row_base + dr < M) d2[(size_t)dr * N] = f2bf(sei_gelu(v[r]));
+                    if (col_ok && row_base + dr < M) d2[(size_t)dr * N] = sei_f2bf(sei_gelu(v[r]));
                 }
             }
             if (d32) {
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16pp_kernel(NtArgs g) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int dr = (r & 3) + 8 * (r >> 2);
-                    if (col_ok && row_base + dr < M) d16[(size_t)dr * N] = f2bf(v[r]);
+                    if (col_ok && row_base + dr < M) d16[(size_t)dr * N] = sei_f2bf(v[r]);
                 }
             }
         }

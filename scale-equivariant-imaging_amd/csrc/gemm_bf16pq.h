@@ -33,24 +33,6 @@
 //        read in the segment after it.
 #pragma once
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <int N>
-__device__ __forceinline__ void pq_wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 13) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-    else if constexpr (N == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-    else static_assert(N < 0, "add the immediate");
-}
 template <int N>
 __device__ __forceinline__ void pq_wait_lgkmcnt() {
     if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
@@ -285,13 +267,13 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
     // at most the pieces issued after the last piece of tile t + 1 stay in flight: B(0), A(0), B(1) of the NS - 1 tiles
     // after it and A(1) of NS - 2 of them
     auto wait_tile = [&](bool full) {
-        if (!full) { pq_wait_vmcnt<0>(); return; }
+        if (!full) { sei_wait_vmcnt<0>(); return; }
         constexpr int LATE_A1 = (NS - 2) * G::NA1;
         if constexpr (G::PA0 % 8 != 0) {
-            if (third) pq_wait_vmcnt<(NS - 1) * (2 * G::NB + G::NA0) + LATE_A1>();
-            else pq_wait_vmcnt<(NS - 1) * (2 * G::NB + G::NA0 - 1) + LATE_A1>();
+            if (third) sei_wait_vmcnt<(NS - 1) * (2 * G::NB + G::NA0) + LATE_A1>();
+            else sei_wait_vmcnt<(NS - 1) * (2 * G::NB + G::NA0 - 1) + LATE_A1>();
         } else {
-            pq_wait_vmcnt<(NS - 1) * (2 * G::NB + G::NA0) + LATE_A1>();
+            sei_wait_vmcnt<(NS - 1) * (2 * G::NB + G::NA0) + LATE_A1>();
         }
     };
 
@@ -406,12 +388,12 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
         };
         // pieces this wave issues per tile: what may stay in flight when tile t must have landed (tile t + 1's)
         auto wait_landed = [&](bool next_in_flight) {
-            if (!next_in_flight) { pq_wait_vmcnt<0>(); return; }
+            if (!next_in_flight) { sei_wait_vmcnt<0>(); return; }
             if constexpr (G::PA0 % 8 != 0) {
-                if (third) pq_wait_vmcnt<2 * G::NB + G::NA0 + G::NA1>();
-                else pq_wait_vmcnt<2 * G::NB + G::NA0 - 1 + G::NA1>();
+                if (third) sei_wait_vmcnt<2 * G::NB + G::NA0 + G::NA1>();
+                else sei_wait_vmcnt<2 * G::NB + G::NA0 - 1 + G::NA1>();
             } else {
-                pq_wait_vmcnt<2 * G::NB + G::NA0 + G::NA1>();
+                sei_wait_vmcnt<2 * G::NB + G::NA0 + G::NA1>();
             }
         };
         issue_tile(0);
@@ -536,7 +518,6 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
 #endif
     if (slabs) {
         constexpr unsigned SLAB_BYTES = (unsigned)G::BM * G::BN * 4u;
-        typedef unsigned pq_u32x4 __attribute__((ext_vector_type(4)));
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             g.ws_slab + (size_t)ord * g.splitk * (G::BM * G::BN), 0, (int)(SLAB_BYTES * (unsigned)g.splitk), 0x00020000);
         const unsigned lane_off = (unsigned)threadIdx.x * 16u;
@@ -545,7 +526,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
         for (int i = 0; i < RF; ++i)
 #pragma unroll
             for (int f = 0; f < NF; ++f)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pq_u32x4, acc[i][f]), rs,
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][f]), rs,
                                                        mine + (unsigned)(i * NF + f) * (NT * 16u) + lane_off, 0, 16);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // EVERY storing wave, before the barrier in front of the ticket
         __syncthreads();
@@ -572,7 +553,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
             const unsigned theirs = (unsigned)sl * SLAB_BYTES + lane_off;
 #pragma unroll
             for (int i0 = 0; i0 < RF; i0 += IB) {
-                pq_u32x4 t[IB][NF];
+                u32x4 t[IB][NF];
 #pragma unroll
                 for (int i = 0; i < IB; ++i)
 #pragma unroll
@@ -698,11 +679,10 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
                 nt_store4(g.adam_v + off[p], vq[p]);
                 nt_store4(g.adam_p + off[p], o);
                 if (g.adam_p16) {
-                    typedef unsigned pq_u32x2 __attribute__((ext_vector_type(2)));
-                    pq_u32x2 t;
-                    t.x = (unsigned)f2bf(o.x) | ((unsigned)f2bf(o.y) << 16);
-                    t.y = (unsigned)f2bf(o.z) | ((unsigned)f2bf(o.w) << 16);
-                    __builtin_nontemporal_store(t, reinterpret_cast<pq_u32x2 *>(g.adam_p16 + off[p]));
+                    u32x2 t;
+                    t.x = sei_pack2_bf16(o.x, o.y);
+                    t.y = sei_pack2_bf16(o.z, o.w);
+                    __builtin_nontemporal_store(t, reinterpret_cast<u32x2 *>(g.adam_p16 + off[p]));
                 }
             }
             continue;
@@ -764,14 +744,14 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
             const size_t o = (size_t)row * N + col;
             if (epi == SEI_EPI_BIAS_GELU) {
                 ushort4 h;
-                h.x = f2bf(sei_gelu_bf16out(v[p][0])); h.y = f2bf(sei_gelu_bf16out(v[p][1]));
-                h.z = f2bf(sei_gelu_bf16out(v[p][2])); h.w = f2bf(sei_gelu_bf16out(v[p][3]));
+                h.x = sei_f2bf(sei_gelu_bf16out(v[p][0])); h.y = sei_f2bf(sei_gelu_bf16out(v[p][1]));
+                h.z = sei_f2bf(sei_gelu_bf16out(v[p][2])); h.w = sei_f2bf(sei_gelu_bf16out(v[p][3]));
                 *reinterpret_cast<ushort4 *>(g.D2_16 + o) = h;
             }
             if (g.D32) *reinterpret_cast<f32x4 *>(g.D32 + o) = v[p];
             if (g.D16) {
                 ushort4 h;
-                h.x = f2bf(v[p][0]); h.y = f2bf(v[p][1]); h.z = f2bf(v[p][2]); h.w = f2bf(v[p][3]);
+                h.x = sei_f2bf(v[p][0]); h.y = sei_f2bf(v[p][1]); h.z = sei_f2bf(v[p][2]); h.w = sei_f2bf(v[p][3]);
                 *reinterpret_cast<ushort4 *>(g.D16 + o) = h;
                 if (g.colsum) {                                   // (uniform) the ROUNDED values, as a pass over D16 would read them
                     csum[0] += __builtin_bit_cast(float, (unsigned)h.x << 16);

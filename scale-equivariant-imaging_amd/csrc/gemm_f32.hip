@@ -19,8 +19,6 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 #ifndef SEI_F32_BK
 #define SEI_F32_BK 32
 #endif

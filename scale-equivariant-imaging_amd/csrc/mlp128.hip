@@ -26,9 +26,6 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
 
@@ -36,10 +33,6 @@ constexpr int WAVES = 9, NT = 64 * WAVES, PX = 16 * WAVES;   // 144 pixels per w
 constexpr int NSTAGE = 4;
 // Per width C (32 or 128): 4 C hidden units in slices of 32; a slice image is 32 x C or C x 32 bf16 = C / 16 pieces of 1 KiB.
 // At C = 32 all four slices (16 KB) fit the ring at once: the same loop, whose late refills then rewrite consumed stages.
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 // ---- LDS-DMA of one 1-KiB piece (p = 0..7) of a slice image; the destination is lane-linear, the source per lane ----
 // "rows" image: 32 rows (hidden units 32 ht ..) x 128 channels of a (512, 128) matrix; 16-byte chunk c of row r sits at
@@ -80,12 +73,6 @@ __device__ __forceinline__ bf16x8 pack_tiles(const f32x4 &t0, const f32x4 &t1) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { a[e] = (__bf16)t0[e]; a[4 + e] = (__bf16)t1[e]; }
     return a;
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -131,8 +118,8 @@ __global__ __launch_bounds__(NT) void mlp128_fwd_kernel(const unsigned short *__
     issue(2);
 #pragma unroll 1
     for (int ht = 0; ht < NSLICE; ++ht) {
-        if (wave < NPC) wait_vmcnt<4>();                            // this wave's pieces of slice ht have landed
-        lds_barrier();                                              // ... everyone's; slice ht - 1 is read out (b2 on the first)
+        if (wave < NPC) sei_wait_vmcnt<4>();                        // this wave's pieces of slice ht have landed
+        sei_lds_barrier();                                          // ... everyone's; slice ht - 1 is read out (b2 on the first)
         issue(ht + 3);                                              // (past the end: into the stage of slice ht - 1, unread)
         const char *st = smem + (ht % NSTAGE) * STAGE;
         // the slice's A fragments in one burst, then the first product; the B fragments of the second product are requested
@@ -148,7 +135,7 @@ __global__ __launch_bounds__(NT) void mlp128_fwd_kernel(const unsigned short *__
         for (int t = 0; t < 2; ++t) {
             hT[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int ks = 0; ks < KS2; ++ks) hT[t] = mfma16(wa[t][ks], f[ks], hT[t]);
+            for (int ks = 0; ks < KS2; ++ks) hT[t] = sei_mfma16(wa[t][ks], f[ks], hT[t]);
         }
         bf16x8 wb[CB];
 #pragma unroll
@@ -163,9 +150,9 @@ __global__ __launch_bounds__(NT) void mlp128_fwd_kernel(const unsigned short *__
             for (int r = 0; r < 4; ++r) hT[t][r] = sei_gelu_bf16out(hT[t][r] + bias[t][r]);
         const bf16x8 a = pack_tiles(hT[0], hT[1]);
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb) acc[cb] = mfma16(a, wb[cb], acc[cb]);
+        for (int cb = 0; cb < CB; ++cb) acc[cb] = sei_mfma16(a, wb[cb], acc[cb]);
     }
-    wait_vmcnt<0>();                                                // the clamped slices still in flight
+    sei_wait_vmcnt<0>();                                            // the clamped slices still in flight
     __syncthreads();                                                // every wave is done with the ring: it becomes the patches
 
     // ---- epilogue through a wave-private patch: accumulators in, whole rows out
@@ -250,12 +237,12 @@ __global__ __launch_bounds__(NT) void mlp128_bwd_kernel(const float *__restrict_
         // three pieces sit, in issue order, [stores ht-3] slice ht+1 [stores ht-2] slice ht+2 [stores ht-1] = 4 + 3 + 4 + 3 + 4
         // operations in the steady state, fewer on the first three slices (nothing was stored before slice 0)
         if (wave < NPC) {
-            if (ht >= 3) wait_vmcnt<18>();
-            else if (ht == 2) wait_vmcnt<14>();
-            else if (ht == 1) wait_vmcnt<10>();
-            else wait_vmcnt<6>();
+            if (ht >= 3) sei_wait_vmcnt<18>();
+            else if (ht == 2) sei_wait_vmcnt<14>();
+            else if (ht == 1) sei_wait_vmcnt<10>();
+            else sei_wait_vmcnt<6>();
         }
-        lds_barrier();
+        sei_lds_barrier();
         issue(ht + 3);
         const char *st = smem + (ht % NSTAGE) * STAGE;
         f32x4 hT[2], gT[2];
@@ -272,8 +259,8 @@ __global__ __launch_bounds__(NT) void mlp128_bwd_kernel(const float *__restrict_
             gT[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS2; ++ks) {
-                hT[t] = mfma16(wa[ks], f[ks], hT[t]);
-                gT[t] = mfma16(wg[ks], g[ks], gT[t]);
+                hT[t] = sei_mfma16(wa[ks], f[ks], hT[t]);
+                gT[t] = sei_mfma16(wg[ks], g[ks], gT[t]);
             }
         }
         bf16x8 wb[CB];                                              // requested before the GELU' arithmetic, which covers them
@@ -302,9 +289,9 @@ __global__ __launch_bounds__(NT) void mlp128_bwd_kernel(const float *__restrict_
         }
         const bf16x8 a = pack_tiles(gT[0], gT[1]);
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb) acc[cb] = mfma16(a, wb[cb], acc[cb]);
+        for (int cb = 0; cb < CB; ++cb) acc[cb] = sei_mfma16(a, wb[cb], acc[cb]);
     }
-    wait_vmcnt<0>();
+    sei_wait_vmcnt<0>();
     __syncthreads();
 
     constexpr int QR = C / 4, ITS = 16 * QR / 64;

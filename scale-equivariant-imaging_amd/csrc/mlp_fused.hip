@@ -27,13 +27,6 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 __device__ __forceinline__ bf16x8 acc_frag(const f32x16 &x, int s) {
     bf16x8 a;
@@ -158,7 +151,7 @@ __global__ __launch_bounds__(THREADS) void mlp_fwd_kernel(const unsigned short *
             for (int s = 0; s < KS; ++s) {
                 const bf16x8 w = row_frag<C>(cur, s, lane);
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) hT[rt] = mfma(w, f[rt][s], hT[rt]);
+                for (int rt = 0; rt < RT; ++rt) hT[rt] = sei_mfma32(w, f[rt][s], hT[rt]);
             }
             float bias[16];
 #pragma unroll
@@ -173,7 +166,7 @@ __global__ __launch_bounds__(THREADS) void mlp_fwd_kernel(const unsigned short *
                 for (int ct = 0; ct < CT; ++ct) {
                     const bf16x8 w = perm_frag<C>(cur + S::ROW_BYTES, ct, s, lane);
 #pragma unroll
-                    for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = mfma(acc_frag(hT[rt], s), w, acc[rt][ct]);
+                    for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = sei_mfma32(acc_frag(hT[rt], s), w, acc[rt][ct]);
                 }
             if (ht + 1 < HT) {                             // the other buffer was last read in iteration ht - 1
                 row_slice_store<C>(nxt, pr);
@@ -267,8 +260,8 @@ __global__ __launch_bounds__(THREADS) void mlp_bwd_kernel(const float *__restric
                 f32x16 hT = {0}, gT = {0};
 #pragma unroll
                 for (int s = 0; s < KS; ++s) {
-                    hT = mfma(row_frag<C>(cur, s, lane), f[rt][s], hT);
-                    gT = mfma(row_frag<C>(cur + S::ROW_BYTES, s, lane), g[rt][s], gT);
+                    hT = sei_mfma32(row_frag<C>(cur, s, lane), f[rt][s], hT);
+                    gT = sei_mfma32(row_frag<C>(cur + S::ROW_BYTES, s, lane), g[rt][s], gT);
                 }
                 // lane = pixel, registers = hidden units: quads of 4 consecutive units -> 8-byte stores
                 const int pix = row0 + 32 * rt + (lane & 31);
@@ -296,7 +289,7 @@ __global__ __launch_bounds__(THREADS) void mlp_bwd_kernel(const float *__restric
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct)
-                        acc[rt][ct] = mfma(acc_frag(gT, s), perm_frag<C>(cur + 2 * S::ROW_BYTES, ct, s, lane), acc[rt][ct]);
+                        acc[rt][ct] = sei_mfma32(acc_frag(gT, s), perm_frag<C>(cur + 2 * S::ROW_BYTES, ct, s, lane), acc[rt][ct]);
             }
             if (ht + 1 < HT) {
                 row_slice_store<C>(nxt, p2);
@@ -319,10 +312,7 @@ __global__ __launch_bounds__(THREADS) void mlp_bwd_kernel(const float *__restric
     }
 }
 
-inline unsigned mlp_grid(int M, int rows_per_group) {
-    size_t g = sei_ceil_div((size_t)M, (size_t)rows_per_group);
-    return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
+inline unsigned mlp_grid(int M, int rows_per_group) { return sei_capped_grid((size_t)M, rows_per_group, 2048); }
 
 }  // namespace
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/sei_hip.h"
+#include "sei_mfma.h"
 
 #define SEI_WAVE 64
 
@@ -16,6 +17,14 @@ static inline int sei_launch_status() { return (int)hipGetLastError(); }
 
 static inline size_t sei_ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 
+// grid of a grid-stride launch: one workgroup per `per_block` items, at least one, at most `cap`
+static inline unsigned sei_capped_grid(size_t work_items, int per_block, unsigned cap) {
+    size_t g = sei_ceil_div(work_items, (size_t)per_block);
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (unsigned)g;
+}
+
 __device__ __forceinline__ int sei_mod(int v, int n) {
     int r = v % n;
     return r < 0 ? r + n : r;
@@ -24,6 +33,13 @@ __device__ __forceinline__ int sei_mod(int v, int n) {
 __device__ __forceinline__ float sei_wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+// Sum over each group of G consecutive lanes (G a power of two <= 64); every lane of the group holds the result.
+template <int G>
+__device__ __forceinline__ float sei_group_sum(float v) {
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
 

@@ -23,11 +23,6 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef short v4s __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ int sb_swz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
 
 struct CmatArgs {

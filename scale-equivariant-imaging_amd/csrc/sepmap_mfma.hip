@@ -2,7 +2,7 @@
 // (reference: src/models/convolutional.py:54-92,113-133 -- the FFT "ideal" resamplers, which are exactly the real
 //  separable rank-2 map  y[b,:,:,c] = L1 X R1^T + L2 X R2^T  (models/_mats.py))
 //
-// The f32 kernels (sepmap_*_packed_kernel, unet_kernels.hip) evaluate the two dense products on packed f32 FMAs and
+// The f32 kernels (sepmap_*_packed_kernel, sepmap_f32.hip) evaluate the two dense products on packed f32 FMAs and
 // are bound by the FMA issue rate (1.36 G FMAs per fine-level call = 35 us at one wave-instruction per 4 cycles).
 // Per image row the W product is a small GEMM  T_t[i] (Wo x C) = R_t (Wo x Wi) . X_i (Wi x C)  and per output column
 // the H product is  Y[:, jo, :] (Ho x C) = [L1 L2] (Ho x 2 Hi) . [T1; T2][:, jo, :] (2 Hi x C): batches of GEMMs with
@@ -38,21 +38,10 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int SMM_WAVES = 12, SMM_THREADS = 64 * SMM_WAVES;
 constexpr int SMM_NC = 16;                        // channels per workgroup = the MFMA's N
 constexpr int SMM_PADK = 8;                       // bf16 elements of padding per K-contiguous LDS row (bank spread)
 constexpr int SMM_LDS = 152 * 1024;
-
-__device__ __forceinline__ unsigned short smm_f2bf(float v) {
-    const __bf16 b = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float smm_bf2f(unsigned short u) {
-    return __builtin_bit_cast(float, (unsigned)u << 16);
-}
 
 struct SmmGeom {
     int B, Hi, Wi, Ho, Wo, C;
@@ -84,9 +73,9 @@ __global__ __launch_bounds__(256) void sepmap_pack_kernel(const float *__restric
             hi_at = g.offL + f;
             lo_at = g.offLlo + f;
         }
-        const unsigned short h = smm_f2bf(v);
+        const unsigned short h = sei_f2bf(v);
         out[hi_at] = h;
-        out[lo_at] = smm_f2bf(v - smm_bf2f(h));
+        out[lo_at] = sei_f2bf(v - sei_bf2f(h));
     }
 }
 
@@ -119,6 +108,8 @@ __global__ __launch_bounds__(SMM_THREADS) void sepmap_mfma_kernel(const float *_
     // Between the passes only LDS has to be settled. __syncthreads() is a workgroup fence first: s_waitcnt vmcnt(0) in
     // front of the s_barrier, i.e. every wave sat out the write latency of its y stores and the whole prefetch of the next
     // image at each barrier (stamped: pass H of the 48 -> 24 map 16 k cycles for two iterations of arithmetic).
+    // Private: wait and barrier are ONE asm statement here; sei_lds_barrier issues the barrier through the builtin, which the
+    // compiler schedules around.
     auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     // Pass H's share of a wave: ONE 16-row tile of the output rows (h_ht) and every h_nk-th output column from h_k on.
     // Its operand from the constant matrices -- rows of [L1 L2], head and remainder -- does not depend on the column or
@@ -222,7 +213,7 @@ __global__ __launch_bounds__(SMM_THREADS) void sepmap_mfma_kernel(const float *_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int jo = jt * 16 + 4 * lg + r;
-                    if (jo < g.Wo) T[((size_t)(t * g.Wo + jo) * SMM_NC + lc) * g.ldT + i] = smm_f2bf(acc[r]);
+                    if (jo < g.Wo) T[((size_t)(t * g.Wo + jo) * SMM_NC + lc) * g.ldT + i] = sei_f2bf(acc[r]);
                 }
             }
         }
@@ -277,7 +268,7 @@ __global__ __launch_bounds__(SMM_THREADS) void sepmap_mfma_kernel(const float *_
         if (io < g.Ho) {
             if (g.out16) {
                 ushort4 h;
-                h.x = smm_f2bf(acc[0]); h.y = smm_f2bf(acc[1]); h.z = smm_f2bf(acc[2]); h.w = smm_f2bf(acc[3]);
+                h.x = sei_f2bf(acc[0]); h.y = sei_f2bf(acc[1]); h.z = sei_f2bf(acc[2]); h.w = sei_f2bf(acc[3]);
                 *reinterpret_cast<ushort4 *>(yb16 + ((size_t)io * g.Wo + jo) * g.C) = h;
             } else {
                 *reinterpret_cast<float4 *>(yb + ((size_t)io * g.Wo + jo) * g.C) = make_float4(acc[0], acc[1], acc[2], acc[3]);

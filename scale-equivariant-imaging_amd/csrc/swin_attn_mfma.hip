@@ -29,11 +29,6 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
-
 constexpr int WS = 8, NTOK = 64, HP = 32, NB = (2 * WS - 1) * (2 * WS - 1), WAVES = 4;
 constexpr int TILE_BYTES = NTOK * HP * 2;                  // one [token][32] bf16 matrix: 4 KiB, 64-byte rows
 
@@ -60,10 +55,6 @@ __device__ __forceinline__ void win_token(const MGeom &g, int win, int i, int &t
 
 __device__ __forceinline__ int bias_bin(int i, int j) {
     return ((i >> 3) - (j >> 3) + WS - 1) * (2 * WS - 1) + ((i & 7) - (j & 7) + WS - 1);
-}
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
 // rows r0 .. r0+31 of a [token][32] tile as the A operand (row = lane & 31) or, equally, as the B operand of the
@@ -195,7 +186,7 @@ __device__ __forceinline__ void scores_T(WaveLds &L, const LaneGeom &G, float sc
         for (int it = 0; it < 2; ++it) {
             f32x16 acc = {0};
 #pragma unroll
-            for (int s = 0; s < 2; ++s) acc = mfma(row_frag(L.k, 32 * jt, s, lane), row_frag(L.q, 32 * it, s, lane), acc);
+            for (int s = 0; s < 2; ++s) acc = sei_mfma32(row_frag(L.k, 32 * jt, s, lane), row_frag(L.q, 32 * it, s, lane), acc);
             p[jt][it] = acc;
         }
     const bool k_low_x = (lane >> 5) == 1;               // key column (r & 3) + 4h >= 4
@@ -280,7 +271,7 @@ __global__ __launch_bounds__(64 * WAVES) void swin_attn_fwd_mfma_kernel(const un
 #pragma unroll
             for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
-                for (int s = 0; s < 2; ++s) o = mfma(acc_frag(p[jt][it], s), tr_frag_perm(L.v, 32 * jt + 16 * s, lane), o);
+                for (int s = 0; s < 2; ++s) o = sei_mfma32(acc_frag(p[jt][it], s), tr_frag_perm(L.v, 32 * jt + 16 * s, lane), o);
             store_tile(L, o, 1.0f, lane, out, C, h * HP, 32 * it, live);
         }
     }
@@ -334,9 +325,9 @@ __device__ __forceinline__ bf16x8 lds_tr_frag(const char *a, const char *b) {
     const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s *)b);
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
+// Private: the pair is built as a vector and converted by one packed instruction; sei_pack2_bf16 builds it with shifts.
 __device__ __forceinline__ unsigned pack2(float a, float b) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)a, (__bf16)b};
+    const bf16x2 v = {(__bf16)a, (__bf16)b};
     return __builtin_bit_cast(unsigned, v);
 }
 // A transposed result tile (rows = head dim on the registers: dims 8 a + 4 h + 0..3 in register quad a; column = token
@@ -358,11 +349,10 @@ __device__ __forceinline__ void store_tile_T(char *stage, const int (&tw)[4], in
     SWIN_LDS_ORDER();
 }
 __device__ __forceinline__ float dot8(uint4 a, uint4 b, float acc) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, a.x), __builtin_bit_cast(bf2, b.x), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, a.y), __builtin_bit_cast(bf2, b.y), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, a.z), __builtin_bit_cast(bf2, b.z), acc, false);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, a.w), __builtin_bit_cast(bf2, b.w), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.x), __builtin_bit_cast(bf16x2, b.x), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.y), __builtin_bit_cast(bf16x2, b.y), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.z), __builtin_bit_cast(bf16x2, b.z), acc, false);
+    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.w), __builtin_bit_cast(bf16x2, b.w), acc, false);
 }
 
 // Rows of a (window, head) as they travel: FOUR lanes per 64-byte token row (lane = 4 * row-in-group + chunk), 16 rows
@@ -474,7 +464,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void swin_attn_bwd_mfma_kernel(
     // is ((iy - jy + 7), (ix - jx + 7)): the sum over the column pairs (ix, jx) with ix - jx = dx is a product of the
     // (bf16) dS tile, read back from LDS as [(iy', jy')][(jx, ix)], with a constant 0 / 1 matrix [(jx, ix)][dx] --
     // two 16x16x32 MFMAs per tile into 4 accumulator registers per (it, jt), 16 in all.
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     f32x4 hsum[2][2] = {{{0}, {0}}, {{0}, {0}}};
     bf16x8 sel[2];
 #pragma unroll
@@ -530,8 +519,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void swin_attn_bwd_mfma_kernel(
                 }
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    s = mfma(lds_frag(L.q + 2048 * it + A.row[ks]), lds_frag(L.k + 2048 * jt + A.row[ks]), s);
-                    dp = mfma(lds_frag(L.g + 2048 * it + A.row[ks]), lds_frag(L.v + 2048 * jt + A.row[ks]), dp);
+                    s = sei_mfma32(lds_frag(L.q + 2048 * it + A.row[ks]), lds_frag(L.k + 2048 * jt + A.row[ks]), s);
+                    dp = sei_mfma32(lds_frag(L.g + 2048 * it + A.row[ks]), lds_frag(L.v + 2048 * jt + A.row[ks]), dp);
                 }
                 // P = exp2(cs S - lse), dS = P (dP - delta); rows of register quad a: queries 32 it + 8 a + 4 hl + 0..3
 #pragma unroll
@@ -559,15 +548,15 @@ __global__ __launch_bounds__(64 * WAVES, 2) void swin_attn_bwd_mfma_kernel(
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const int t0 = 64 * (32 * it + 16 * ks);
-                    dvt[jt] = mfma(lds_tr_frag(L.g + t0 + A.tr[0], L.g + t0 + A.tr[1]), pf[ks], dvt[jt]);
-                    dkt[jt] = mfma(lds_tr_frag(L.q + t0 + A.tr[0], L.q + t0 + A.tr[1]), df[ks], dkt[jt]);
+                    dvt[jt] = sei_mfma32(lds_tr_frag(L.g + t0 + A.tr[0], L.g + t0 + A.tr[1]), pf[ks], dvt[jt]);
+                    dkt[jt] = sei_mfma32(lds_tr_frag(L.q + t0 + A.tr[0], L.q + t0 + A.tr[1]), df[ks], dkt[jt]);
                 }
                 SWIN_LDS_ORDER();
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const int t0 = 64 * (32 * jt + 16 * ks);
-                    dqt = mfma(lds_tr_frag(L.k + t0 + A.tr[0], L.k + t0 + A.tr[1]),
-                               lds_tr_frag(L.t + 1024 * ks + A.tr[0], L.t + 1024 * ks + A.tr[1]), dqt);
+                    dqt = sei_mfma32(lds_tr_frag(L.k + t0 + A.tr[0], L.k + t0 + A.tr[1]),
+                                     lds_tr_frag(L.t + 1024 * ks + A.tr[0], L.t + 1024 * ks + A.tr[1]), dqt);
                 }
                 // bias gradient: hsum[it][jt][(iy', jy')][dx] += sum over (ix, jx) of dS [ix - jx == dx]
 #pragma unroll

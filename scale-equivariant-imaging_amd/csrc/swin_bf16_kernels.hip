@@ -15,22 +15,14 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned short f2bf(float v) {
-    const __bf16 b = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, b);
-}
-
-inline unsigned stream_grid(size_t items, int per_block) {
-    size_t g = sei_ceil_div(items, (size_t)per_block);
-    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
+inline unsigned stream_grid(size_t items, int per_block) { return sei_capped_grid(items, per_block, 4096); }
 
 __global__ __launch_bounds__(256) void pack_kernel(const float *__restrict__ src, const int *__restrict__ map,
                                                     void *__restrict__ dst, size_t n, int to_bf16) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int m = map[i];
         const float v = m >= 0 ? src[m] : 0.f;
-        if (to_bf16) reinterpret_cast<unsigned short *>(dst)[i] = f2bf(v);
+        if (to_bf16) reinterpret_cast<unsigned short *>(dst)[i] = sei_f2bf(v);
         else reinterpret_cast<float *>(dst)[i] = v;
     }
 }
@@ -79,10 +71,10 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_pad_kernel(const float *__res
         if (4 * lane < ldy) {
             ushort4 o = make_ushort4(pad0, 0, 0, 0);
             if (live) {
-                o.x = f2bf(dx * rs * gm.x + bt.x);
-                o.y = f2bf(dy * rs * gm.y + bt.y);
-                o.z = f2bf(dz * rs * gm.z + bt.z);
-                o.w = f2bf(dw * rs * gm.w + bt.w);
+                o.x = sei_f2bf(dx * rs * gm.x + bt.x);
+                o.y = sei_f2bf(dy * rs * gm.y + bt.y);
+                o.z = sei_f2bf(dz * rs * gm.z + bt.z);
+                o.w = sei_f2bf(dw * rs * gm.w + bt.w);
             }
             reinterpret_cast<ushort4 *>(y + row * ldy)[lane] = o;
         }
@@ -205,7 +197,7 @@ __global__ __launch_bounds__(256) void cast_pad_bf16_kernel(const float *__restr
             acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
         }
         if (4 * lane < ldy)
-            reinterpret_cast<ushort4 *>(y + row * ldy)[lane] = make_ushort4(f2bf(v.x), f2bf(v.y), f2bf(v.z), f2bf(v.w));
+            reinterpret_cast<ushort4 *>(y + row * ldy)[lane] = make_ushort4(sei_f2bf(v.x), sei_f2bf(v.y), sei_f2bf(v.z), sei_f2bf(v.w));
     }
     if (colsum) {                                          // here: per-workgroup partials [workgroup][C]
         red[wave][lane] = acc;
@@ -240,7 +232,7 @@ __global__ __launch_bounds__(256) void pad_nhwc_bf16_kernel(const float *__restr
             const size_t b = p / ((size_t)Wp * Hp);
             if (x >= 1 && x <= W && y >= 1 && y <= H) {
                 const float4 v = reinterpret_cast<const float4 *>(src + ((b * H + (y - 1)) * W + (x - 1)) * C)[c];
-                o = make_ushort4(f2bf(v.x), f2bf(v.y), f2bf(v.z), f2bf(v.w));
+                o = make_ushort4(sei_f2bf(v.x), sei_f2bf(v.y), sei_f2bf(v.z), sei_f2bf(v.w));
             }
         }
         reinterpret_cast<ushort4 *>(dst)[e] = o;

@@ -272,10 +272,7 @@ __global__ __launch_bounds__(256) void rowscale_kernel(const float *__restrict__
     }
 }
 
-inline unsigned stream_grid(size_t items) {
-    size_t g = sei_ceil_div(items, 256);
-    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
+inline unsigned stream_grid(size_t items) { return sei_capped_grid(items, 256, 4096); }
 
 inline int check_geom(int B, int H, int W, int heads, int hd, int shift) {
     SEI_REQUIRE(B > 0 && H >= WS && W >= WS && H % WS == 0 && W % WS == 0 && heads > 0);

@@ -23,12 +23,8 @@
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // 16-B chunk swizzle of a [64 tokens][64 columns] image (128-B rows, two per 256-B bank row): as gemm_bf16pq.h
 __device__ __forceinline__ int tg_swz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
@@ -367,24 +363,6 @@ constexpr int RG_EPI_SCALE_RES_LN = 103;
 constexpr int RG_EPI_GELU16 = 104;    // SEI_EPI_BIAS_GELU without the float32 pre-activation: bias + GELU in the accumulator
                                       // layout, bf16 patch, 16-byte stores; small enough for TWO workgroups per CU
 
-template <int N>
-__device__ __forceinline__ void rg_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is six bits");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// LDS writes of this wave done, then the barrier (a bare s_barrier does not wait for them; __syncthreads would also
-// wait for every global load and LDS-DMA piece in flight)
-__device__ __forceinline__ void rg_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
-
-__device__ __forceinline__ unsigned rg_pack2(float a, float b) {
-    const __bf16 x = (__bf16)a, y = (__bf16)b;
-    return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
-
 // EPI: the SEI_EPI_* code; OUT16: SEI_EPI_NONE / _BIAS write bf16 (else float32)
 // Wave layout: 8 = WN (column groups) x WR (row groups) x WK (halves of K). WK = 2 only where a wave's slice of W would
 // not fit otherwise (K = 576): the two partial sums then meet in the patch. NBT 16-column blocks are dealt to the WN
@@ -634,9 +612,9 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
     // ---- prologue: tile 0 and its auxiliary rows landed, tile 1 in flight
     issue(0);
     issue(1);
-    if (P % 8 != 0 && wave < P % 8) rg_wait_vmcnt<NDMA_HI>();
-    else rg_wait_vmcnt<NDMA_LO>();
-    rg_lds_barrier();
+    if (P % 8 != 0 && wave < P % 8) sei_wait_vmcnt<NDMA_HI>();
+    else sei_wait_vmcnt<NDMA_LO>();
+    sei_lds_barrier();
 
     for (int t = 0; t < nt; ++t) {
         float *const patch = PATCH2 ? reinterpret_cast<float *>(reinterpret_cast<char *>(patch0) + (t & 1) * PATCH_ONE) : patch0;
@@ -711,8 +689,8 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
         }
         }
         // tile t + 1 (issued one iteration ago) and everything older have landed; what this iteration issued may fly
-        if (P % 8 != 0 && wave < P % 8) rg_wait_vmcnt<NAUX + NDMA_HI>();
-        else rg_wait_vmcnt<NAUX + NDMA_LO>();
+        if (P % 8 != 0 && wave < P % 8) sei_wait_vmcnt<NAUX + NDMA_HI>();
+        else sei_wait_vmcnt<NAUX + NDMA_LO>();
         // ---- accumulators into the patch (WK = 2: the second half of K adds to the first)
         if constexpr (P16 && !GELU16 && !TWO) {
             unsigned short *pw16 = reinterpret_cast<unsigned short *>(patch) + (wr * RB * 16 + 4 * lg) * LDP16 + 16 * nb0 + l16;
@@ -741,7 +719,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
                     for (int j = 0; j < 4; ++j) pw[(16 * rb + j) * LDP + 16 * nb] = acc[rb][nb][j];
                 }
         }
-        rg_lds_barrier();
+        sei_lds_barrier();
         if constexpr (WK == 2) {
             if (wk == 1) {
 #pragma unroll
@@ -751,15 +729,15 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
 #pragma unroll
                         for (int j = 0; j < 4; ++j) pw[(16 * rb + j) * LDP + 16 * nb] += acc[rb][nb][j];
             }
-            rg_lds_barrier();
+            sei_lds_barrier();
         }
         // ---- rows out: the tile's auxiliary rows have landed when only this iteration's DMA pieces are in flight. The wait
         // first, between scheduling fences, and only then a use of the registers that the compiler can see: a copy it
         // makes for that use then reads landed data (tied to the wait itself, the copy was placed in front of it)
         if constexpr (HAS_ROWS) {
             __builtin_amdgcn_sched_barrier(0);
-            if (P % 8 != 0 && wave < P % 8) rg_wait_vmcnt<NDMA_HI>();
-            else rg_wait_vmcnt<NDMA_LO>();
+            if (P % 8 != 0 && wave < P % 8) sei_wait_vmcnt<NDMA_HI>();
+            else sei_wait_vmcnt<NDMA_LO>();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < QPT; ++i) {
@@ -770,8 +748,8 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
         const size_t row0 = (size_t)(b + t * G) * TR;
         if constexpr (LNF) {
             __builtin_amdgcn_sched_barrier(0);
-            if (P % 8 != 0 && wave < P % 8) rg_wait_vmcnt<NDMA_HI>();
-            else rg_wait_vmcnt<NDMA_LO>();
+            if (P % 8 != 0 && wave < P % 8) sei_wait_vmcnt<NDMA_HI>();
+            else sei_wait_vmcnt<NDMA_LO>();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 3; ++k) asm volatile("" : "+v"(lx[k]));
@@ -822,15 +800,15 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
                     y[0] = 1.0f;
                 }
                 uint2 h;
-                h.x = rg_pack2(y[0], y[1]);
-                h.y = rg_pack2(y[2], y[3]);
+                h.x = sei_pack2_bf16(y[0], y[1]);
+                h.y = sei_pack2_bf16(y[2], y[3]);
                 *reinterpret_cast<uint2 *>(g.D16 + row * g.ld16 + 4 * qk) = h;
             }
         }
         if constexpr (LNB) {
             __builtin_amdgcn_sched_barrier(0);
-            if (P % 8 != 0 && wave < P % 8) rg_wait_vmcnt<NDMA_HI>();
-            else rg_wait_vmcnt<NDMA_LO>();
+            if (P % 8 != 0 && wave < P % 8) sei_wait_vmcnt<NDMA_HI>();
+            else sei_wait_vmcnt<NDMA_LO>();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -883,8 +861,8 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
                     for (int j = 0; j < 4; ++j) ys[j] = valid ? o[j] * lsc : 0.f;
                     if constexpr (KT != 9) ac[k] += ys;              // (K = 576: no registers left for the third column sum)
                     uint2 h;
-                    h.x = rg_pack2(ys[0], ys[1]);
-                    h.y = rg_pack2(ys[2], ys[3]);
+                    h.x = sei_pack2_bf16(ys[0], ys[1]);
+                    h.y = sei_pack2_bf16(ys[2], ys[3]);
                     *reinterpret_cast<uint2 *>(g.D16 + row * g.ld16 + 4 * qk) = h;
                 }
             }
@@ -927,21 +905,21 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
 #pragma unroll
                 for (int j = 0; j < 4; ++j) ge[j] = qc + j == g.gelu_one_at ? 1.0f : sei_gelu_bf16out(v[0][j]);
                 uint2 h;
-                h.x = rg_pack2(ge[0], ge[1]);
-                h.y = rg_pack2(ge[2], ge[3]);
+                h.x = sei_pack2_bf16(ge[0], ge[1]);
+                h.y = sei_pack2_bf16(ge[2], ge[3]);
                 *reinterpret_cast<uint2 *>(g.D16 + row * g.ld16 + qc) = h;
             } else if constexpr (GQ == 2) {
                 uint4 h;
-                h.x = rg_pack2(v[0][0], v[0][1]);
-                h.y = rg_pack2(v[0][2], v[0][3]);
-                h.z = rg_pack2(v[GQ - 1][0], v[GQ - 1][1]);
-                h.w = rg_pack2(v[GQ - 1][2], v[GQ - 1][3]);
+                h.x = sei_pack2_bf16(v[0][0], v[0][1]);
+                h.y = sei_pack2_bf16(v[0][2], v[0][3]);
+                h.z = sei_pack2_bf16(v[GQ - 1][0], v[GQ - 1][1]);
+                h.w = sei_pack2_bf16(v[GQ - 1][2], v[GQ - 1][3]);
                 *reinterpret_cast<uint4 *>(g.D16 + row * g.ld16 + qc) = h;
             }
         }
-        if constexpr (!PATCH2) rg_lds_barrier();          // the patch and stage t % 3 are free again
+        if constexpr (!PATCH2) sei_lds_barrier();         // the patch and stage t % 3 are free again
     }
-    rg_wait_vmcnt<0>();                                   // the clamped stages still in flight
+    sei_wait_vmcnt<0>();                                  // the clamped stages still in flight
     if constexpr (LNB) {
         // column sums of this workgroup: [3][32 rows][48 quads] through the (now idle) ring, then 3 x 48 threads add up
         // the 32 rows in a fixed order; [workgroup][3][nv] partials, folded by sei_fold_partials3

@@ -96,7 +96,7 @@ def resample_matrices(kind, H, W, rate, device):
     return _DEVICE_CACHE[key]
 
 
-SM_PAD = 24          # padding of the output axis in the packed layouts (csrc/unet_kernels.hip)
+SM_PAD = 24          # padding of the output axis in the packed layouts (csrc/sepmap_f32.hip)
 
 
 def pack_for_kernel(mats, device):
