@@ -82,8 +82,7 @@ class FlatParameterBucket:
         _ops.register_gradient_range(self, grads)       # backward functions find this model's bookkeeping by address
         # bf16 copy of the whole bucket for the throughput mode (written by the fused Adam kernel)
         self.flat_shadow = torch.zeros(total, dtype=torch.bfloat16, device=dev) if dev.type == "cuda" else None
-        # validity of the bf16 bucket is tracked per model: {"gen": generation it was written for,
-        # "version": torch version counter of each parameter at that time}
+        # validity of the bf16 bucket is tracked per model (models/_shadow.ShadowState)
         self._sei_plain_state = _ops._new_plain_state()
         self._sei_zero_ranges = None
         for p, off in zip(params, offsets):

@@ -9,6 +9,7 @@ import os
 import torch
 
 import _native as N
+from ._shadow import split_x2
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_MUL_DGELU, EPI_ACCUM, EPI_BIAS_ROWSCALE = range(7)
 
@@ -93,41 +94,6 @@ def gemm(A, Bm, M, Nn, K, ta, tb, epi, out=None, bias=None, R1=None, R2=None, D2
     _gemm_call(2.0 * M * Nn * K, _GEMM_ENTRY[get_compute_dtype()] or "sei_gemm_f32_ex", A.data_ptr(), Bm.data_ptr(), out.data_ptr(), M, Nn, K,
                ta, tb, epi, N.ptr(bias), N.ptr(R1), N.ptr(R2), N.ptr(D2), 1, 0, 0, 0, int(allow_splitk))
     return out
-
-
-# ---------------------------------------------------------------------------------------------
-# weight generations: when a cached bf16 copy of a weight (shadow, transposed shadow, bf16x3 planes) is still current
-# ---------------------------------------------------------------------------------------------
-_GLOBAL_GENERATION = 0      # bumped by weights_updated() without a model: every model's cached bf16 copies are suspect
-
-
-def _new_plain_state():
-    """Validity of a model's bf16 bucket (`flat_shadow`), tracked PER MODEL: "wgen" = this model's weight generation
-    (bumped whenever its parameters change behind torch's version counters: its own optimizer kernel, its own
-    load_state_dict), "gen" = the (global, own) generation pair the bf16 bucket was last written for, "version" = torch's
-    version counter of each parameter at that time, "stale" = (start, stop) of the bucket whose float32 masters are OUT OF
-    DATE on this rank (sharded optimizer step: only the bf16 copies of other ranks' shares were gathered) or None."""
-    return {"gen": None, "wgen": 0, "version": {}, "stale": None}
-
-
-def _generation(plain):
-    return (_GLOBAL_GENERATION, plain["wgen"] if plain is not None else 0)
-
-
-def weights_updated(backbone=None, plain_shadow_written=False):
-    """Parameters changed outside torch's version counters. With a `backbone` only THAT model's cached bf16 copies are
-    invalidated (another model's optimizer step or load_state_dict must not make this one recast its weights: under a
-    sharded optimizer step the float32 masters of other ranks' shares are stale and a recast would overwrite good bf16
-    weights with old values); without one, every model's. `plain_shadow_written`: the optimizer kernel also refreshed
-    `backbone.flat_shadow` (the bf16 copy of every parameter), so that copy is current for the new generation."""
-    global _GLOBAL_GENERATION
-    if backbone is None:
-        _GLOBAL_GENERATION += 1
-        return
-    plain = backbone._sei_plain_state
-    plain["wgen"] += 1
-    if plain_shadow_written:
-        plain["gen"] = _generation(plain)
 
 
 # Split-K workspace of the quadrant GEMM (sei_gemm_bf16nt_ws, include/sei_hip.h): tile counters in its first 16 KiB (zero
@@ -320,25 +286,6 @@ def _x3_ok(A, Bm, M, Nn, K, ta, tb, epi, out=None, R1=None, D2=None):
     if not N.aligned(A, Bm, out, R1 if epi == EPI_MUL_DGELU else None, D2 if epi == EPI_BIAS_GELU else None):
         return False
     return epi in (EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_MUL_DGELU, EPI_ACCUM, EPI_BIAS_ROWSCALE)
-
-
-def split_x2(t):
-    """(2, *t.shape) bf16: head and remainder planes of a float32 tensor. A parameter's planes are cached until its
-    values change (this model's optimizer kernel / load_state_dict: `_generation`, torch's version counter) -- and rebuilt
-    once inside a capture, so that every replay splits the weights of ITS step."""
-    def fresh():
-        planes = torch.empty((2,) + tuple(t.shape), dtype=torch.bfloat16, device=t.device)
-        N.call("sei_split_bf16x2", t.data_ptr(), planes.data_ptr(), t.numel())
-        return planes
-    if not isinstance(t, torch.nn.Parameter):
-        return fresh()
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (_generation(getattr(t, "_sei_plain_state", None)), t._version, t.data_ptr(), capturing)
-    hit = getattr(t, "_sei_split", None)
-    if hit is None or hit[0] != key:
-        hit = (key, fresh())
-        t._sei_split = hit
-    return hit[1]
 
 
 def gemm_x3(A, Bm, M, Nn, K, ta, tb, epi, out, bias=None, R1=None, R2=None, D2=None):

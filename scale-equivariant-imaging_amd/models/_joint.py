@@ -32,6 +32,8 @@ import os
 
 import torch
 
+from ._gemm import joint_rows
+
 ENABLED = os.environ.get("SEI_NO_JOINT_BACKWARD") != "1"
 KEEP_ARENA = os.environ.get("SEI_KEEP_ARENA") == "1"       # bench.py's roofline leg re-issues a step's launches afterwards: their operands must stay allocated
 
@@ -212,8 +214,29 @@ def _finish(rec, backbone):
             _walk(rec, backbone, (call,))
 
 
+def joint_ctx(fn, c1, c2, rec):
+    """The ctx of a layer's backward over both calls: saved activations as 3B-row tensors (rec.joint raises where two
+    tensors are not the two parts of one arena buffer). Every layer function that tapes itself says how (models/_ops.py);
+    one that does not has no joint form."""
+    build = getattr(fn, "joint_ctx", None)
+    if build is None:
+        raise _NotJoint()
+    return build(c1, c2, rec)
+
+
+def walk_backward(fns, ctxs, go):
+    """Play a model call's tape (the layer functions in forward order, with their ctx -- or joint ctx --) backwards from
+    the gradient of the model output. The U-Net is a chain plus skip connections nested like brackets: an Upsample's skip
+    gradient waits on the `skips` stack for the Downsample that handed the skip on (their `walk` methods)."""
+    skips = []
+    g = go
+    for fn, ctx in zip(reversed(fns), reversed(ctxs)):
+        if g is None:
+            break
+        g = fn.walk(ctx, g, skips)
+
+
 def _walk(rec, backbone, which):
-    from . import _ops
     joint = len(which) == 2
     tapes = [rec.tapes[c] for c in which]
     if joint and (len(tapes[0]) != len(tapes[1]) or any(a[0] is not b[0] for a, b in zip(*tapes))):
@@ -226,7 +249,7 @@ def _walk(rec, backbone, which):
         rec.done[c] = True
     if joint:
         try:
-            ctxs = [_ops.joint_ctx(fn, c1, c2, rec) for (fn, c1), (_, c2) in zip(*tapes)]
+            ctxs = [joint_ctx(fn, c1, c2, rec) for (fn, c1), (_, c2) in zip(*tapes)]
         except _NotJoint:
             rec.done[which[0]] = rec.done[which[1]] = False
             _walk(rec, backbone, (which[0],))
@@ -241,8 +264,8 @@ def _walk(rec, backbone, which):
         ctxs = [c for _, c in tapes[0]]
         go = rec.parked[which[0]]
         fns = [fn for fn, _ in tapes[0]]
-    with _ops.joint_rows(backbone, (rec.batch[0], rec.batch[1]) if joint else None):
-        _ops.walk_backward(fns, ctxs, go)
+    with joint_rows(backbone, (rec.batch[0], rec.batch[1]) if joint else None):
+        walk_backward(fns, ctxs, go)
     for c in which:                                          # the layer nodes and their saved activations may go
         rec.outputs[c] = None
         rec.tapes[c] = []

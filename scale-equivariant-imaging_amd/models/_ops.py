@@ -12,15 +12,17 @@ import torch
 
 import _native as N
 from . import _mats, _wgrad
-# (the GEMM dispatch and the weight-gradient scheduler are modules of their own; the names the rest of the package, the
-# tests and the tools reach through this module are imported here. The switches DWSTREAM, DEFERRED_FOLDS and
-# TOKEN_STREAMING are read where they live, models/_wgrad.py: assign them there)
+# (the GEMM dispatch, the cached bf16 weight copies and the weight-gradient scheduler are modules of their own; the names
+# the rest of the package, the tests and the tools reach through this module are imported here. The switches DWSTREAM,
+# DEFERRED_FOLDS and TOKEN_STREAMING are read where they live, models/_wgrad.py: assign them there)
 from ._gemm import (EPI_ACCUM, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_BIAS_ROWSCALE, EPI_MUL_DGELU, EPI_NONE,  # noqa: F401
-                    SPLITK_COUNTER_BYTES, SPLITK_WS_MIB, SPLITK_WS_STREAMS, _SPLITK_WS, _gemm_call, _generation,
-                    _in_forward_mode, _new_plain_state, compute_dtype_scope, gemm, gemm_mixed, gemm_nt16, gemm_x3,
-                    get_compute_dtype, joint_rows, own_splitk_workspace, profile_gemms, release_splitk_workspace,
-                    reset_splitk_counters, set_compute_dtype, split_x2, splitk_workspace, weights_updated)
-from ._joint import JointCtx, _NotJoint
+                    SPLITK_COUNTER_BYTES, SPLITK_WS_MIB, SPLITK_WS_STREAMS, _SPLITK_WS, _gemm_call, _in_forward_mode,
+                    compute_dtype_scope, gemm, gemm_mixed, gemm_nt16, gemm_x3, get_compute_dtype, joint_rows,
+                    own_splitk_workspace, profile_gemms, release_splitk_workspace, reset_splitk_counters, set_compute_dtype,
+                    splitk_workspace)
+from ._joint import JointCtx, _NotJoint, joint_ctx, walk_backward  # noqa: F401
+from ._shadow import (ShadowState, _new_plain_state, _transposed16, _transposed16_cached, plain_shadow_is_current,  # noqa: F401
+                      refresh_plain_shadow, set_stale_masters, shadow, split_x2, weights_updated)
 from ._wgrad import (_state_for, begin_step, colsum16_into, defer_fold, direct_bf16_launches, flush_weight_grads,  # noqa: F401
                      fused_adam_launches, merged_weight_grads, note_forward, register_gradient_range,
                      set_direct_bf16_grads, set_fused_adam, set_weight_grad_merging, set_weight_grad_milestone, state_of,
@@ -241,6 +243,20 @@ def _nhwc(x):
 # `twice` adds the block input a second time: the encoder's inner residual x + xb with xb == x
 # (convolutional.py:226-231) fused into the last GEMM's epilogue.
 # ---------------------------------------------------------------------------------------------
+def _convblock_tail(ctx, x, h1, mean, rstd, gh2, go):
+    """The end of every ConvBlock backward, from the gradient gh2 of the LayerNorm's output: LayerNorm backward, depthwise
+    weight gradient, flipped depthwise data gradient with the residual's `go` (twice over when the block input was added
+    twice) in its epilogue."""
+    w1, b1, gamma, beta = ctx.params[:4]
+    B, H, W, C = x.shape
+    gh1 = layer_norm_bwd(h1.view(B * H * W, C), gamma, mean, rstd, gh2, grad_of(gamma), grad_of(beta)).view(B, H, W, C)
+    dwconv7_weight_grad(x, gh1, grad_of(w1), grad_of(b1))
+    gx = None
+    if ctx.needs_input_grad[0]:
+        gx = dwconv7(gh1, w1, None, flip=True, res=go, res_scale=2.0 if ctx.twice else 1.0)
+    return (gx,) + (None,) * 9
+
+
 class ConvBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, gamma, beta, w2, b2, w3, b3, twice):
@@ -274,14 +290,51 @@ class ConvBlockFn(torch.autograd.Function):
         colsum_into(grad_of(b2), gh3)
         gemm(gh3, h2, 4 * C, C, M, 1, 0, EPI_ACCUM, out=grad_of(w2).view(4 * C, C))
         gh2 = gemm(gh3, w2, M, C, 4 * C, 0, 0, EPI_NONE)
-        # LayerNorm, depthwise conv
-        gh1 = layer_norm_bwd(h1.view(M, C), gamma, mean, rstd, gh2, grad_of(gamma), grad_of(beta))
-        gh1 = gh1.view(B, H, W, C)
-        dwconv7_weight_grad(x, gh1, grad_of(w1), grad_of(b1))
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = dwconv7(gh1, w1, None, flip=True, res=go, res_scale=2.0 if ctx.twice else 1.0)
-        return (gx,) + (None,) * 9
+        return _convblock_tail(ctx, x, h1, mean, rstd, gh2, go)
+
+
+# ---------------------------------------------------------------------------------------------
+# What the float32 and the bf16 class of a resampling layer share: shapes and matrices, the skip check, and the end of
+# the backward. `resample` is the class's own resampler (sepmap2 / sepmap2_16); the other launches are the same for both.
+# ---------------------------------------------------------------------------------------------
+def _resample_prologue(kind, x, w, rate):
+    """(B, H, W, C, Co, fwd, bwd, Ho, Wo) of a resampling layer on the NHWC input x with the 1x1 weight w."""
+    B, H, W, C = x.shape
+    fwd, bwd = _mats.resample_matrices(kind, H, W, rate, x.device)
+    return B, H, W, C, w.shape[0], fwd, bwd, fwd[0].shape[0], fwd[1].shape[0]
+
+
+def _downsample_tail(ctx, gu, gskip, resample):
+    """From the gradient gu (Mo, C) of the resampler's output: its adjoint, then the LayerNorm backward with the skip
+    connection's gradient added in the same kernel."""
+    x, mean, rstd = ctx.saved_tensors[:3]
+    gamma, beta = ctx.params[:2]
+    B, H, W, C = x.shape
+    M = B * H * W
+    gh = resample(gu.view(B, ctx.hw[2], ctx.hw[3], C), ctx.mats_t, H, W).view(M, C)
+    res = None if gskip is None else gskip.contiguous().view(M, C)
+    gx = layer_norm_bwd(x.view(M, C), gamma, mean, rstd, gh, grad_of(gamma), grad_of(beta), res=res).view(B, H, W, C)
+    return (gx if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
+
+
+def _check_skip(skip, shape):
+    skip = _nhwc(skip)
+    if tuple(skip.shape) != shape:
+        raise ValueError("skip connection shape mismatch")
+    return skip
+
+
+def _upsample_tail(ctx, go, gh, resample):
+    """From the gradient gh (M, C) of the LayerNorm's output: LayerNorm backward, the resampler's adjoint; the skip
+    connection's gradient is `go` itself."""
+    u, mean, rstd = ctx.saved_tensors[:3]
+    gamma, beta = ctx.params[:2]
+    gu = layer_norm_bwd(u.view(-1, u.shape[-1]), gamma, mean, rstd, gh, grad_of(gamma), grad_of(beta))
+    gx = None
+    if ctx.needs_input_grad[0]:
+        gx = resample(gu.view(u.shape), ctx.mats_t, *ctx.in_hw)
+    gskip = go if ctx.needs_input_grad[1] else None
+    return gx, gskip, None, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -304,11 +357,8 @@ class DownsampleFn(torch.autograd.Function):
         ctx.dtype = get_compute_dtype()
         ctx.set_materialize_grads(False)
         x = _nhwc(x)
-        B, H, W, C = x.shape
-        M, Co = B * H * W, w.shape[0]
-        h, mean, rstd = layer_norm(x.view(M, C), gamma, beta)
-        fwd, bwd = _mats.resample_matrices("down", H, W, rate, x.device)
-        Ho, Wo = fwd[0].shape[0], fwd[1].shape[0]
+        h, mean, rstd = layer_norm(x.view(-1, x.shape[-1]), gamma, beta)
+        B, H, W, C, Co, fwd, bwd, Ho, Wo = _resample_prologue("down", x, w, rate)
         u = sepmap2(h.view(B, H, W, C), fwd, Ho, Wo)
         Mo = B * Ho * Wo
         s = _mats.constant_response("down", H, W, rate, x.device, B)
@@ -322,17 +372,12 @@ class DownsampleFn(torch.autograd.Function):
     def backward(ctx, go, gskip=None):
         x, mean, rstd, u, s = ctx.saved_tensors
         gamma, beta, w, b = ctx.params
-        B, H, W, C = x.shape
-        Ho, Wo = ctx.hw[2], ctx.hw[3]
-        M, Mo, Co = B * H * W, B * Ho * Wo, w.shape[0]
+        Mo, (Co, C) = x.shape[0] * ctx.hw[2] * ctx.hw[3], w.shape[:2]
         go2 = go.contiguous().view(Mo, Co)
         colsum_into(grad_of(b), go2, row_weight=s)
         gemm(go2, u.view(Mo, C), Co, C, Mo, 1, 0, EPI_ACCUM, out=grad_of(w).view(Co, C))
         gu = gemm(go2, w, Mo, C, Co, 0, 0, EPI_NONE)
-        gh = sepmap2(gu.view(B, Ho, Wo, C), ctx.mats_t, H, W).view(M, C)
-        res = None if gskip is None else gskip.contiguous().view(M, C)
-        gx = layer_norm_bwd(x.view(M, C), gamma, mean, rstd, gh, grad_of(gamma), grad_of(beta), res=res).view(B, H, W, C)
-        return (gx if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
+        return _downsample_tail(ctx, gu, gskip, sepmap2)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -344,18 +389,12 @@ class UpsampleFn(torch.autograd.Function):
         _no_joint_form()
         ctx.dtype = get_compute_dtype()
         x = _nhwc(x)
-        B, H, W, C = x.shape
-        Co = w.shape[0]
-        fwd, bwd = _mats.resample_matrices("up", H, W, rate, x.device)
-        Ho, Wo = fwd[0].shape[0], fwd[1].shape[0]
+        B, H, W, C, Co, fwd, bwd, Ho, Wo = _resample_prologue("up", x, w, rate)
         u = sepmap2(x, fwd, Ho, Wo)
         M = B * Ho * Wo
         h, mean, rstd = layer_norm(u.view(M, C), gamma, beta)
         if skip is not None:
-            skip = _nhwc(skip)
-            if tuple(skip.shape) != (B, Ho, Wo, Co):
-                raise ValueError("skip connection shape mismatch")
-            out = gemm(h, w, M, Co, C, 0, 1, EPI_BIAS_RES, bias=b, R1=skip)
+            out = gemm(h, w, M, Co, C, 0, 1, EPI_BIAS_RES, bias=b, R1=_check_skip(skip, (B, Ho, Wo, Co)))
         else:
             out = gemm(h, w, M, Co, C, 0, 1, EPI_BIAS, bias=b)
         ctx.save_for_backward(u, mean, rstd, h)
@@ -373,12 +412,7 @@ class UpsampleFn(torch.autograd.Function):
         colsum_into(grad_of(b), go2)
         gemm(go2, h, Co, C, M, 1, 0, EPI_ACCUM, out=grad_of(w).view(Co, C))
         gh = gemm(go2, w, M, C, Co, 0, 0, EPI_NONE)
-        gu = layer_norm_bwd(u.view(M, C), gamma, mean, rstd, gh, grad_of(gamma), grad_of(beta))
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = sepmap2(gu.view(B, Ho, Wo, C), ctx.mats_t, *ctx.in_hw)
-        gskip = go if ctx.needs_input_grad[1] else None
-        return gx, gskip, None, None, None, None, None
+        return _upsample_tail(ctx, go, gh, sepmap2)
 
 
 # =============================================================================================
@@ -388,66 +422,6 @@ class UpsampleFn(torch.autograd.Function):
 # register-staged kernel on the bf16 tensors and accumulate into the f32 gradient bucket. Everything
 # else (depthwise conv, LayerNorm statistics and backward, resamplers, residuals, Adam) stays f32.
 # =============================================================================================
-def plain_shadow_is_current(backbone):
-    return backbone._sei_plain_state["gen"] == _generation(backbone._sei_plain_state)
-
-
-def set_stale_masters(backbone, span):
-    """optim.FlatAdam (sharded step): float32 parameters inside bucket range `span` are stale on this rank until
-    `consolidate()`; None clears it. While set, nothing may rebuild bf16 copies of that range from the masters."""
-    backbone._sei_plain_state["stale"] = None if span is None else (int(span[0]), int(span[1]))
-
-
-def _stale_error():
-    return RuntimeError("the float32 weights of other ranks' shares are out of date on this rank (sharded optimizer step: "
-                        "only their bf16 copies were all-gathered) and something asked for bf16 copies to be rebuilt from "
-                        "them; call optimizer.consolidate() on every rank before changing or re-reading the weights")
-
-
-def refresh_plain_shadow(backbone):
-    """Cast the whole flat parameter bucket to its bf16 copy (what the fused Adam does as a side output)."""
-    if getattr(backbone, "flat_shadow", None) is None:
-        return
-    if backbone._sei_plain_state["stale"] is not None:
-        raise _stale_error()
-    N.call("sei_cast_bf16", backbone.flat_params.data_ptr(), backbone.flat_shadow.data_ptr(),
-           backbone.flat_params.numel())
-    plain = backbone._sei_plain_state
-    plain["gen"] = _generation(plain)
-
-
-def shadow(p):
-    """bf16 copy w16 (R,C) of a 1x1-conv weight p (R,C,1,1): a view of the owning model's flat bf16 bucket,
-    which the fused Adam kernel rewrites every step; cast here only when that copy is not current.
-    (No transposed copy exists: the data-gradient GEMM reads w16 reduction-major.)"""
-    plain = getattr(p, "_sei_plain_state", None)
-    key = (_generation(plain), p._version, p.data_ptr())
-    st = getattr(p, "_sei_shadow", None)
-    if st is None or st[0] != key:
-        R, C = p.shape[0], p.shape[1]
-        flat16 = getattr(p, "_sei_shadow_view", None)
-        if st is not None and st[1].device == p.device:
-            w16 = st[1]
-        else:
-            w16 = flat16.view(R, C) if flat16 is not None else torch.empty((R, C), dtype=torch.bfloat16, device=p.device)
-        # the bucket copy is current when it was written for this generation and torch has not changed p since it was
-        # last looked at here
-        plain_current = (flat16 is not None and plain is not None and plain["gen"] == key[0]
-                         and plain["version"].get(id(p)) == p._version)
-        if not plain_current:
-            stale = plain["stale"] if plain is not None else None
-            if stale is not None:
-                off = getattr(p, "_sei_bucket_offset", None)
-                if off is None or (off < stale[1] and stale[0] < off + p.numel()):
-                    raise _stale_error()
-            N.call("sei_cast_bf16", p.data_ptr(), w16.data_ptr(), p.numel())
-        if plain is not None:
-            plain["version"][id(p)] = p._version
-        st = (key, w16)
-        p._sei_shadow = st
-    return st[1]
-
-
 def nt16_ok(K):
     return K % 8 == 0
 
@@ -516,55 +490,10 @@ def fused_mlp_ok(M, C):
     return C in FUSED_MLP_CHANNELS and N.lib().sei_mlp_fused_eligible(M, C) != 0
 
 
-def _transposed16_cached(p, w16):
-    """_transposed16 of a weight's bf16 copy, rebuilt only when the copy changed (one optimizer step = one rebuild, not
-    one per backward function: the step's two model calls share it). Every weight that has ever asked is remembered per
-    model; when one of them is stale, ALL stale ones are rebuilt by one sei_transpose_bf16_many launch (the 8 matrices of the
-    two fused levels: one launch per step instead of 8 of ~9 us each)."""
-    plain = getattr(p, "_sei_plain_state", None)
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (_generation(plain), p._version, w16.data_ptr())
-    hit = getattr(p, "_sei_shadow_t", None)
-    if hit is not None and hit[0] == key and hit[2] == capturing:
-        return hit[1]
-    group = plain.setdefault("transposed", {}) if plain is not None else {}
-    group[id(p)] = (p, w16)
-    stale = []
-    for q, q16 in group.values():
-        qkey = (_generation(plain), q._version, q16.data_ptr())
-        qhit = getattr(q, "_sei_shadow_t", None)
-        if qhit is None or qhit[0] != qkey or qhit[2] != capturing:
-            # another weight rides along only while its bf16 copy in the bucket is known to be current (`shadow`'s own
-            # test); anything else is rebuilt when its layer asks, after `shadow` has had its look
-            if q is p or (plain is not None and plain["gen"] == qkey[0] and plain["version"].get(id(q)) == q._version):
-                stale.append((q, q16, qkey))
-    if len(stale) == 1 or not p.is_cuda:
-        hit = (key, _transposed16(w16), capturing)
-        p._sei_shadow_t = hit
-        return hit[1]
-    for k in range(0, len(stale), N.TRANSPOSE_MAX_JOBS):
-        part = stale[k:k + N.TRANSPOSE_MAX_JOBS]
-        outs = [torch.empty((q16.shape[1], q16.shape[0]), dtype=torch.bfloat16, device=q16.device) for _, q16, _ in part]
-        jobs = (N.TransposeJob * len(part))(*[N.TransposeJob(q16.data_ptr(), o.data_ptr(), q16.shape[0], q16.shape[1])
-                                             for (_, q16, _), o in zip(part, outs)])
-        N.call("sei_transpose_bf16_many", jobs, len(part))
-        for (q, _, qkey), o in zip(part, outs):
-            q._sei_shadow_t = (qkey, o, capturing)
-    return p._sei_shadow_t[1]
-
-
-def _transposed16(w16):
-    """(R, C) bf16 -> (C, R) bf16 copy (data movement; the fused MLP backward reads both weights transposed)."""
-    R, C = w16.shape
-    wt = torch.empty((C, R), dtype=torch.bfloat16, device=w16.device)
-    N.call("sei_cast_transpose_bf16", w16.data_ptr(), 1, None, wt.data_ptr(), R, C, R, None)
-    return wt
-
-
 class ConvBlockFn16(torch.autograd.Function):
-    """ConvBlockFn with bf16 storage of h2 / h4 / gh3 and the direct-to-LDS GEMMs (C % 64 == 0). At the shallow
-    levels (C in FUSED_MLP_CHANNELS) conv2 -> GELU -> conv3 + residual is ONE launch whose 4C-wide hidden activation
-    never reaches HBM (sei_mlp_fused_fwd); the backward recomputes it (sei_mlp_fused_bwd)."""
+    """ConvBlockFn with bf16 storage of h2 / h4 / gh3 and the direct-to-LDS GEMMs (C % 32 == 0: `use_bf16_blocks`). At
+    the shallow levels (C in FUSED_MLP_CHANNELS) conv2 -> GELU -> conv3 + residual is ONE launch whose 4C-wide hidden
+    activation never reaches HBM (sei_mlp_fused_fwd); the backward recomputes it (sei_mlp_fused_bwd)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, gamma, beta, w2, b2, w3, b3, twice):
@@ -581,16 +510,15 @@ class ConvBlockFn16(torch.autograd.Function):
             # counted with the GEMM family (roofline leg): 2 GEMMs of M x 4C x C
             _gemm_call(4.0 * M * 4 * C * C, "sei_mlp_fused_fwd", h2.data_ptr(), w2_16.data_ptr(), b2.data_ptr(),
                        w3_16.data_ptr(), b3.data_ptr(), x.data_ptr(), 2.0 if twice else 1.0, out.data_ptr(), M, C)
-            ctx.save_for_backward(x, h1, mean, rstd, h2)
-            ctx.params = (w1, b1, gamma, beta, w2, b2, w3, b3)
-            ctx.twice = twice
-            return out.view(B, H, W, C)
-        h3 = _alloc((M, 4 * C), torch.float32, x.device)
-        h4 = _alloc((M, 4 * C), torch.bfloat16, x.device)
-        gemm_nt16(h2, w2_16, M, 4 * C, C, EPI_BIAS_GELU, out32=h3, bias=b2, D2_16=h4)
-        out = _alloc((M, C), torch.float32, x.device)
-        gemm_nt16(h4, w3_16, M, C, 4 * C, EPI_BIAS_RES, out32=out, bias=b3, R1=x, R2=x if twice else None)
-        ctx.save_for_backward(x, h1, mean, rstd, h2, h3, h4)
+            saved = (x, h1, mean, rstd, h2)
+        else:
+            h3 = _alloc((M, 4 * C), torch.float32, x.device)
+            h4 = _alloc((M, 4 * C), torch.bfloat16, x.device)
+            gemm_nt16(h2, w2_16, M, 4 * C, C, EPI_BIAS_GELU, out32=h3, bias=b2, D2_16=h4)
+            out = _alloc((M, C), torch.float32, x.device)
+            gemm_nt16(h4, w3_16, M, C, 4 * C, EPI_BIAS_RES, out32=out, bias=b3, R1=x, R2=x if twice else None)
+            saved = (x, h1, mean, rstd, h2, h3, h4)
+        ctx.save_for_backward(*saved)
         ctx.params = (w1, b1, gamma, beta, w2, b2, w3, b3)
         ctx.twice = twice
         return out.view(B, H, W, C)
@@ -615,13 +543,7 @@ class ConvBlockFn16(torch.autograd.Function):
         gh2 = torch.empty((M, C), dtype=torch.float32, device=x.device)
         gemm_nt16(gh3, shadow(w2), M, C, 4 * C, EPI_NONE, out32=gh2, b_rmajor=True)
         weight_grad16(gh3, h2, grad_of(w2).view(4 * C, C))
-        gh1 = layer_norm_bwd(h1.view(M, C), gamma, mean, rstd, gh2, grad_of(gamma), grad_of(beta)).view(B, H, W, C)
-        dwconv7_weight_grad(x, gh1, grad_of(w1), grad_of(b1))
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = dwconv7(gh1, w1, None, flip=True, res=go, res_scale=2.0 if ctx.twice else 1.0)
-        return (gx,) + (None,) * 9
-
+        return _convblock_tail(ctx, x, h1, mean, rstd, gh2, go)
 
     @staticmethod
     def _backward_fused(ctx, go):
@@ -649,12 +571,17 @@ class ConvBlockFn16(torch.autograd.Function):
             colsum16_into(grad_of(b2), gh3)
             weight_grad16(go16, h4, grad_of(w3).view(C, 4 * C))
             weight_grad16(gh3, h2, grad_of(w2).view(4 * C, C))
-        gh1 = layer_norm_bwd(h1.view(M, C), gamma, mean, rstd, gh2, grad_of(gamma), grad_of(beta)).view(B, H, W, C)
-        dwconv7_weight_grad(x, gh1, grad_of(w1), grad_of(b1))
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = dwconv7(gh1, w1, None, flip=True, res=go, res_scale=2.0 if ctx.twice else 1.0)
-        return (gx,) + (None,) * 9
+        return _convblock_tail(ctx, x, h1, mean, rstd, gh2, go)
+
+    @staticmethod
+    def joint_ctx(c1, c2, rec):
+        if c1.fused != c2.fused or c1.twice != c2.twice:
+            raise _NotJoint()
+        return JointCtx(c1, [rec.joint(a, b) for a, b in zip(c1.saved_tensors, c2.saved_tensors)])
+
+    @staticmethod
+    def walk(ctx, g, skips):
+        return ConvBlockFn16.backward(ctx, g)[0]
 
 
 class DownsampleFn16(torch.autograd.Function):
@@ -665,11 +592,8 @@ class DownsampleFn16(torch.autograd.Function):
         ctx.dtype = get_compute_dtype()
         ctx.set_materialize_grads(False)
         x = _nhwc(x)
-        B, H, W, C = x.shape
-        M, Co = B * H * W, w.shape[0]
-        h, mean, rstd = layer_norm(x.view(M, C), gamma, beta)
-        fwd, bwd = _mats.resample_matrices("down", H, W, rate, x.device)
-        Ho, Wo = fwd[0].shape[0], fwd[1].shape[0]
+        h, mean, rstd = layer_norm(x.view(-1, x.shape[-1]), gamma, beta)
+        B, H, W, C, Co, fwd, bwd, Ho, Wo = _resample_prologue("down", x, w, rate)
         u = sepmap2_16(h.view(B, H, W, C), fwd, Ho, Wo, out16=True)
         Mo = B * Ho * Wo
         s = _mats.constant_response("down", H, W, rate, x.device, B)
@@ -687,18 +611,26 @@ class DownsampleFn16(torch.autograd.Function):
     def backward(ctx, go, gskip=None):
         x, mean, rstd, u16, s = ctx.saved_tensors
         gamma, beta, w, b = ctx.params
-        B, H, W, C = x.shape
-        Ho, Wo = ctx.hw[2], ctx.hw[3]
-        M, Mo, Co = B * H * W, B * Ho * Wo, w.shape[0]
+        Mo, (Co, C) = x.shape[0] * ctx.hw[2] * ctx.hw[3], w.shape[:2]
         go2 = go.contiguous().view(Mo, Co)
         go16 = cast16(go2, colsum_into_=grad_of(b), row_weight=s)           # (the bias gradient from the cast's own pass)
         gu = torch.empty((Mo, C), dtype=torch.float32, device=x.device)
         gemm_nt16(go16, shadow(w), Mo, C, Co, EPI_NONE, out32=gu, b_rmajor=True)
         weight_grad16(go16, u16, grad_of(w).view(Co, C))           # after the data gradient: see ConvBlockFn16.backward
-        gh = sepmap2_16(gu.view(B, Ho, Wo, C), ctx.mats_t, H, W).view(M, C)
-        res = None if gskip is None else gskip.contiguous().view(M, C)
-        gx = layer_norm_bwd(x.view(M, C), gamma, mean, rstd, gh, grad_of(gamma), grad_of(beta), res=res).view(B, H, W, C)
-        return (gx if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
+        return _downsample_tail(ctx, gu, gskip, sepmap2_16)
+
+    @staticmethod
+    def joint_ctx(c1, c2, rec):
+        (x1, *mid1, _), (x2, *mid2, _) = c1.saved_tensors, c2.saved_tensors
+        x = rec.joint(x1, x2)
+        s = _mats.constant_response("down", c1.hw[0], c1.hw[1], c1.rate, x.device, x.shape[0])
+        return JointCtx(c1, [x] + [rec.joint(a, b) for a, b in zip(mid1, mid2)] + [s])
+
+    @staticmethod
+    def walk(ctx, g, skips):
+        """The gradient of the skip this layer handed on was pushed by the Upsample that received it."""
+        gskip = skips.pop() if ctx.with_skip and skips else None
+        return DownsampleFn16.backward(ctx, g, gskip)[0]
 
 
 class UpsampleFn16(torch.autograd.Function):
@@ -706,10 +638,7 @@ class UpsampleFn16(torch.autograd.Function):
     def forward(ctx, x, skip, gamma, beta, w, b, rate):
         ctx.dtype = get_compute_dtype()
         x = _nhwc(x)
-        B, H, W, C = x.shape
-        Co = w.shape[0]
-        fwd, bwd = _mats.resample_matrices("up", H, W, rate, x.device)
-        Ho, Wo = fwd[0].shape[0], fwd[1].shape[0]
+        B, H, W, C, Co, fwd, bwd, Ho, Wo = _resample_prologue("up", x, w, rate)
         u = sepmap2_16(x, fwd, Ho, Wo)
         M = B * Ho * Wo
         h, mean, rstd = layer_norm16(u.view(M, C), gamma, beta)
@@ -717,10 +646,7 @@ class UpsampleFn16(torch.autograd.Function):
         out = _alloc((M, Co), torch.float32, x.device)
         _tape(UpsampleFn16, ctx)
         if skip is not None:
-            skip = _nhwc(skip)
-            if tuple(skip.shape) != (B, Ho, Wo, Co):
-                raise ValueError("skip connection shape mismatch")
-            gemm_nt16(h, w16, M, Co, C, EPI_BIAS_RES, out32=out, bias=b, R1=skip)
+            gemm_nt16(h, w16, M, Co, C, EPI_BIAS_RES, out32=out, bias=b, R1=_check_skip(skip, (B, Ho, Wo, Co)))
         else:
             gemm_nt16(h, w16, M, Co, C, EPI_BIAS, out32=out, bias=b)
         ctx.save_for_backward(u, mean, rstd, h)
@@ -739,12 +665,18 @@ class UpsampleFn16(torch.autograd.Function):
         gh = torch.empty((M, C), dtype=torch.float32, device=u.device)
         gemm_nt16(go16, shadow(w), M, C, Co, EPI_NONE, out32=gh, b_rmajor=True)
         weight_grad16(go16, h, grad_of(w).view(Co, C))             # after the data gradient: see ConvBlockFn16.backward
-        gu = layer_norm_bwd(u.view(M, C), gamma, mean, rstd, gh, grad_of(gamma), grad_of(beta))
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = sepmap2_16(gu.view(B, Ho, Wo, C), ctx.mats_t, *ctx.in_hw)
-        gskip = go if ctx.needs_input_grad[1] else None
-        return gx, gskip, None, None, None, None, None
+        return _upsample_tail(ctx, go, gh, sepmap2_16)
+
+    @staticmethod
+    def joint_ctx(c1, c2, rec):
+        return JointCtx(c1, [rec.joint(a, b) for a, b in zip(c1.saved_tensors, c2.saved_tensors)])
+
+    @staticmethod
+    def walk(ctx, g, skips):
+        """The skip's gradient waits on the stack for the Downsample that handed the skip on."""
+        gx, gskip = UpsampleFn16.backward(ctx, g)[:2]
+        skips.append(gskip)
+        return gx
 
 
 # ---------------------------------------------------------------------------------------------
@@ -795,46 +727,10 @@ class Conv3x3Fn(torch.autograd.Function):
         gres = go if ctx.needs_input_grad[3] else None
         return gx, None, None, gres, None, None
 
+    @staticmethod
+    def joint_ctx(c1, c2, rec):
+        return JointCtx(c1, [rec.joint(c1.saved_tensors[0], c2.saved_tensors[0])], cfg=(c1.cfg[0] + c2.cfg[0],) + c1.cfg[1:])
 
-# ---------------------------------------------------------------------------------------------
-# One backward pass for the step's two model calls (models/_joint.py): joint ctx of each layer function, the walk
-# ---------------------------------------------------------------------------------------------
-def joint_ctx(fn, c1, c2, rec):
-    """The ctx of a layer's backward over both calls: saved activations as 3B-row tensors (rec.joint raises where two
-    tensors are not the two parts of one arena buffer)."""
-    s1, s2 = c1.saved_tensors, c2.saved_tensors
-    if fn is Conv3x3Fn:
-        B, H, W, Ci, Co, nchw_in, nchw_out = c1.cfg
-        return JointCtx(c1, [rec.joint(s1[0], s2[0])], cfg=(B + c2.cfg[0], H, W, Ci, Co, nchw_in, nchw_out))
-    if fn is ConvBlockFn16:
-        if c1.fused != c2.fused or c1.twice != c2.twice:
-            raise _NotJoint()
-        return JointCtx(c1, [rec.joint(a, b) for a, b in zip(s1, s2)])
-    if fn is DownsampleFn16:
-        x = rec.joint(s1[0], s2[0])
-        H, W = c1.hw[0], c1.hw[1]
-        s = _mats.constant_response("down", H, W, c1.rate, x.device, x.shape[0])
-        return JointCtx(c1, [x, rec.joint(s1[1], s2[1]), rec.joint(s1[2], s2[2]), rec.joint(s1[3], s2[3]), s])
-    if fn is UpsampleFn16:
-        return JointCtx(c1, [rec.joint(a, b) for a, b in zip(s1, s2)])
-    raise _NotJoint()
-
-
-def walk_backward(fns, ctxs, go):
-    """Play a model call's tape (the layer functions in forward order, with their ctx -- or joint ctx --) backwards from
-    the gradient of the model output. The U-Net is a chain plus skip connections nested like brackets: an Upsample's skip
-    gradient waits on a stack for the Downsample that handed the skip on."""
-    skips = []
-    g = go
-    for fn, ctx in zip(reversed(fns), reversed(ctxs)):
-        if g is None:
-            break
-        if fn is UpsampleFn16:
-            outs = fn.backward(ctx, g)
-            g = outs[0]
-            skips.append(outs[1])
-        elif fn is DownsampleFn16:
-            gskip = skips.pop() if ctx.with_skip and skips else None
-            g = fn.backward(ctx, g, gskip)[0]
-        else:
-            g = fn.backward(ctx, g)[0]
+    @staticmethod
+    def walk(ctx, g, skips):
+        return Conv3x3Fn.backward(ctx, g)[0]

@@ -44,8 +44,8 @@ class FlatAdam(torch.optim.Optimizer):
     @property
     def _master_stale(self):
         """Sharded step, bf16 mode: the float32 weights of other ranks' shares are out of date on this rank (kept on the
-        backbone, where models/_ops refuses to rebuild bf16 copies from them until `consolidate()`)."""
-        return self.backbone._sei_plain_state["stale"] is not None
+        backbone, where models/_shadow refuses to rebuild bf16 copies from them until `consolidate()`)."""
+        return self.backbone._sei_plain_state.stale is not None
 
     def zero_grad(self, set_to_none=True):
         self.backbone.zero_grad_flat()
@@ -144,7 +144,7 @@ class FlatAdam(torch.optim.Optimizer):
         from models import _ops
         red = self.reducer
         flat = self.backbone.flat_params
-        stale = self.backbone._sei_plain_state["stale"]
+        stale = self.backbone._sei_plain_state.stale
         for k in red.order:
             s, e = red.bounds[k]
             red.wait(k)

@@ -736,3 +736,56 @@ def test_oracle_shift_mask_is_the_published_calculate_mask(H, W):
         assert torch.equal(coord, attn_mask), (H, W, shift)
         if H == ws:
             assert float(region.min()) >= 3                     # no region 0 .. 2: every window is a last-row window
+
+
+def test_shadow_state_decides_when_a_bf16_copy_is_current():
+    """models/_shadow.ShadowState on plain parameters: what a weight-generation bump, torch's version counters, the global
+    bump and the stale range of a sharded optimizer step each do to "this bf16 copy may be used as it is"."""
+    from models import _shadow
+    from models._shadow import ShadowState
+    a, b = ShadowState(), ShadowState()
+    assert _shadow._new_plain_state is ShadowState and a.stale is None and a.transposed == {}
+    p, q = torch.nn.Parameter(torch.zeros(4, 2, 1, 1)), torch.nn.Parameter(torch.zeros(3))
+    for state in (a, b):
+        for t in (p, q):
+            state.note_version(t)
+    assert not a.is_current() and not a.bucket_copy_current(p)          # nothing has written the bucket yet
+    a.mark_current()
+    b.mark_current()
+    assert a.is_current() and a.bucket_copy_current(p) and a.bucket_copy_current(q)
+    gen = a.generation()
+    a.bump()                                                            # parameters changed, bf16 bucket not rewritten
+    assert a.generation() != gen and not a.is_current() and not a.bucket_copy_current(p)
+    assert b.is_current() and b.bucket_copy_current(p)                  # ... and model B is left alone
+    a.bump(plain_shadow_written=True)                                   # the optimizer kernel rewrote the bucket as well
+    assert a.is_current() and a.bucket_copy_current(p) and a.bucket_copy_current(q)
+    with torch.no_grad():
+        p.add_(1.0)                                                     # torch changed p behind the bucket's back
+    assert not a.bucket_copy_current(p) and a.bucket_copy_current(q)
+    assert not a.bucket_copy_current(torch.nn.Parameter(torch.zeros(2)))    # never looked at
+    a.note_version(p)
+    assert a.bucket_copy_current(p)
+
+    class Model:
+        pass
+    model = Model()
+    model._sei_plain_state = a
+    _shadow.weights_updated(model, plain_shadow_written=True)
+    assert a.is_current() and b.is_current() and _shadow.plain_shadow_is_current(model)
+    _shadow.weights_updated(model)
+    assert not a.is_current() and b.is_current()
+    a.mark_current()
+    _shadow.weights_updated()                                           # no model: every state is suspect
+    assert not a.is_current() and not b.is_current() and not a.bucket_copy_current(q) and not b.bucket_copy_current(q)
+
+    # the stale range of a sharded step: [offset, offset + numel) against [start, stop)
+    p._sei_bucket_offset, numel = 64, p.numel()
+    assert numel == 8 and not a.stale_overlaps(p)
+    for span, hit in [((0, 64), False), ((0, 65), True), ((72, 100), False), ((71, 100), True), ((66, 67), True),
+                      ((0, 1000), True), ((64, 72), True), ((0, 10), False), ((100, 200), False)]:
+        _shadow.set_stale_masters(model, span)
+        assert a.stale == span and a.stale_overlaps(p) is hit, span
+    assert a.stale_overlaps(q)                                          # no known offset: it may lie inside
+    assert "consolidate()" in str(a.stale_error())
+    a.set_stale(None)
+    assert a.stale is None and not a.stale_overlaps(p) and not a.stale_overlaps(q)
