@@ -42,7 +42,7 @@ extern "C" {
  *   U-Net (f32)  sei_conv3x3_fwd, sei_conv3x3_bwd_weight, sei_dwconv7_fwd, sei_dwconv7_bwd_weight (+ _workspace),
  *                sei_ln_fwd, sei_ln_bwd (+ sei_ln_bwd_workspace), sei_gemm_f32, sei_colsum_f32, sei_sepmap2
  *   U-Net (bf16) sei_cast_bf16, sei_ln_fwd_bf16, sei_gemm_bf16nt
- *   optimizer    sei_adam_fused
+ *   optimizer    sei_adam_fused, sei_sgd_fused (+ sei_sgd_partials, sei_sgd_penalty_finish)
  *   baselines    sei_tv_prox (+ sei_tv_prox_work_floats)
  * INTERNAL -- everything else in this header: fused, schedule-specific (_ex, _ws, _dw2*, _plan, _eligible, _parts,
  * _count ...), SwinIR and measurement entry points that this build's own host layer (models/_ops.py, graphs.py, optim.py,
@@ -780,6 +780,28 @@ int sei_adam_scalars(float lr, float beta1, float beta2, float eps, float weight
  * a captured step: stream-ordered, nothing on the host to overwrite while the GPU lags behind) */
 int sei_adam_scalars_to_device(float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                float *dev6, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fine-tuning step (demo/train.py:157-186 with --fine_tuning; src/losses/weights_distance_loss.py): torch.optim.SGD
+ * without momentum over elements [lo, hi) of one flat bucket, with the weights-distance penalty
+ * lambd * sum_k mean((anchor_k - p_k)^2) / K and its gradient folded into the same pass. All pointers are the BUCKET's
+ * (element 0), 16-byte aligned (param_bf16: 8). Per element, float32:
+ *   d = p - anchor;  g' = grad_scale * g + 2 c d;  penalty += c d d (the p before the update);  p -= lr g'
+ * and param_bf16 (optional) receives the bf16 copy of the updated p. coef64[b] = c = lambd / (K n_k) of the parameter
+ * that owns elements [64 b, 64 b + 64): every parameter starts on a 64-element boundary of the bucket and the padding
+ * (zero in every bucket: d = 0) changes nothing. anchor, coef64 and partials are given together or not at all (then
+ * d = 0: plain SGD). lo, hi: multiples of 4, and of 64 with an anchor; anything else, NULL or misaligned pointers and an
+ * empty range are SEI_ERR_BAD_ARG and nothing is launched.
+ * The penalty is reproducible bit for bit: no float atomics; workgroup w writes its sum to partials[w] (double,
+ * sei_sgd_partials(lo, hi, grid_cap) of them; 0 = arguments sei_sgd_fused refuses), and sei_sgd_penalty_finish -- one
+ * workgroup -- adds `count` consecutive partials (of one or several sei_sgd_fused launches) in index order in double and
+ * stores one float32 on the device. grid_cap: 0 = the library's grid (one two-quad trip per thread up to 2^20
+ * workgroups), > 0 = at most that many workgroups, which then loop (tests, tools/exp_sgd.py). Same weights either way.
+ * ------------------------------------------------------------------------------------------- */
+size_t sei_sgd_partials(size_t lo, size_t hi, int grid_cap);
+int sei_sgd_fused(float *param, const float *grad, const float *anchor, const float *coef64, size_t lo, size_t hi,
+                  float lr, float grad_scale, uint16_t *param_bf16, double *partials, int grid_cap, void *stream);
+int sei_sgd_penalty_finish(const double *partials, size_t count, float *penalty, void *stream);
 
 /* The same two-segment weight gradient STORED as bf16 (whole-row 8-byte quads): with several GPUs and a bf16-compressed
  * gradient exchange the gradient is written straight into the exchange buffer (parallel.FlatGradientReducer.comm) --

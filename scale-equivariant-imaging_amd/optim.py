@@ -1,5 +1,8 @@
-"""Fused Adam over the model's flat parameter bucket (replaces torch.optim.Adam at demo/train.py:157-186
-for the U-Net; same update rule, one kernel launch per chunk instead of a foreach sweep per tensor).
+"""Fused optimizers over the model's flat parameter bucket.
+
+FlatAdam replaces torch.optim.Adam at demo/train.py:157-186 (same update rule, one kernel launch per chunk instead of a
+foreach sweep per tensor); FlatSGD replaces the fine-tuning path's torch.optim.SGD together with the weights-distance
+penalty that the reference adds to the loss before backward() (demo/train.py:245-266, src/losses/weights_distance_loss.py).
 
 Keeps a torch.optim.Optimizer-compatible surface (param_groups with "lr", state_dict / load_state_dict,
 zero_grad, step) so the reference's schedulers and checkpoint code drive it unchanged. `state_dict()` is
@@ -286,3 +289,114 @@ class FlatAdam(torch.optim.Optimizer):
                    None if shadow is None else shadow[s:e].data_ptr())
         # bf16 weight shadows must be rebuilt before the next forward (the plain copy just was, if asked)
         _ops.weights_updated(self.backbone, plain_shadow_written=shadow is not None)
+
+
+def coefficient_table(model, lambd=1.0):
+    """One float per 64-element block of the model's flat bucket: c = lambd / (K * n_k) on every block of parameter k (K
+    named parameters of `model`, n_k elements in the k-th), 0 elsewhere. The weights-distance penalty
+    lambd * sum_k mean((anchor_k - p_k)^2) / K is then sum_i c_i d_i^2 over the bucket and its gradient 2 c_i d_i. Built on
+    the host (a CPU tensor); every parameter starts on a 64-element boundary of the bucket (models/_flat.py)."""
+    backbone = model.get_backbone() if hasattr(model, "get_backbone") else model
+    total = backbone.flat_params.numel()
+    named = list(model.named_parameters())
+    if total % 64:
+        raise ValueError("the flat bucket is not a whole number of 64-element blocks")
+    table = torch.zeros(total // 64, dtype=torch.float32)
+    for name, p in named:
+        off = getattr(p, "_sei_bucket_offset", None)
+        if off is None or off % 64:
+            raise ValueError(f"{name} does not start on a 64-element boundary of the flat bucket")
+        table[off // 64:(off + p.numel() + 63) // 64] = float(lambd) / (len(named) * p.numel())
+    return table
+
+
+class FlatSGD(torch.optim.Optimizer):
+    """torch.optim.SGD without momentum over the flat bucket, one sei_sgd_fused launch per range, with the reference's
+    WeightsDistanceLoss folded in: with `anchor=True` the weights at construction (after --weights were loaded: the
+    reference's deepcopy at that point) are kept, the penalty's gradient is added to the step and its value -- from the
+    weights BEFORE the update, as the reference adds it to the loss before backward() -- is left in `last_penalty`
+    (0-dim, on the device; zero without an anchor). `only`: parameter names; the step then covers their 64-aligned
+    bucket ranges alone and nothing else is read or written, the bf16 copy included (K stays the number of ALL named
+    parameters: a frozen parameter never leaves its anchor, its term is zero). Gradients are read from `flat_grads` as
+    they stand: under several GPUs the caller has reduced and averaged them (train.py's generic path)."""
+
+    def __init__(self, model, lr, anchor=None, lambd=1.0, only=None, grid_cap=0):
+        backbone = model.get_backbone() if hasattr(model, "get_backbone") else model
+        if getattr(backbone, "flat_params", None) is None:
+            raise ValueError("FlatSGD needs a model whose parameters live in one flat bucket")
+        self.backbone = backbone
+        flat = backbone.flat_params
+        if only is None:
+            self._named = list(model.parameters())    # the order torch.optim.SGD(model.parameters()) indexes by
+            self._ranges = [(0, flat.numel())]
+        else:
+            self._named = [model.get_parameter(key) for key in only]
+            self._ranges = sorted((p._sei_bucket_offset, p._sei_bucket_offset + (p.numel() + 63) // 64 * 64)
+                                  for p in self._named)
+        if any(lo % 64 or hi % 64 or hi > flat.numel() for lo, hi in self._ranges):
+            raise ValueError("FlatSGD: a parameter range is not made of whole 64-element blocks of the flat bucket")
+        super().__init__([flat], dict(lr=lr))
+        self.lambd = float(lambd)
+        self.grid_cap = int(grid_cap)                 # 0: the library's grid (tests and tools/exp_sgd.py pass others)
+        self.anchor = self.coef64 = self._partials = None
+        self.last_penalty = torch.zeros((), dtype=torch.float32, device=flat.device)
+        if anchor:
+            self.anchor = flat.detach().clone()
+            self.coef64 = coefficient_table(model, lambd).to(flat.device)
+
+    def zero_grad(self, set_to_none=True):
+        self.backbone.zero_grad_flat()
+
+    # -- checkpoint interchange ----------------------------------------------------------------
+    def _torch_group(self):
+        """torch.optim.SGD's own group (its keys and defaults in this torch) at this optimizer's settings."""
+        group = torch.optim.SGD([torch.zeros(1)], lr=self.param_groups[0]["lr"]).state_dict()["param_groups"][0]
+        group.update({k: v for k, v in self.param_groups[0].items() if k != "params"})
+        group["params"] = list(range(len(self._named)))
+        return group
+
+    def state_dict(self):
+        """torch.optim.SGD's layout over the parameters the reference passes it (all of model.parameters(), or the
+        `only` ones): no momentum, so `state` is empty."""
+        return {"state": {}, "param_groups": [self._torch_group()]}
+
+    def load_state_dict(self, state_dict):
+        groups = state_dict["param_groups"]
+        count = sum(len(g["params"]) for g in groups)
+        if len(groups) != 1 or count != len(self._named):
+            raise ValueError(f"optimizer state has {len(groups)} group(s) over {count} parameters; this optimizer steps "
+                             f"{len(self._named)} parameters in one group (a torch.optim.SGD state over the same "
+                             "parameters is expected)")
+        group = groups[0]
+        if any(e.get("momentum_buffer") is not None for e in state_dict["state"].values()) or group.get("momentum"):
+            raise ValueError("SGD states with momentum are not supported by the fused optimizer")
+        if group.get("nesterov") or group.get("maximize") or group.get("weight_decay"):
+            raise ValueError("nesterov / maximize / weight_decay SGD states are not supported by the fused optimizer")
+        known = self._torch_group()
+        self.param_groups[0].update({k: v for k, v in group.items()
+                                     if k != "params" and (k not in known or k in self.param_groups[0])})
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from models import _ops
+        backbone = self.backbone
+        flat, grads = backbone.flat_params, backbone.flat_grads
+        N.check_tensor(flat, "flat_params")
+        N.check_tensor(grads, "flat_grads")
+        shadow = getattr(backbone, "flat_shadow", None) if _ops.get_compute_dtype(backbone) == "bf16" else None
+        if shadow is not None and self._ranges != [(0, flat.numel())] and not _ops.plain_shadow_is_current(backbone):
+            _ops.refresh_plain_shadow(backbone)       # this step writes its own ranges of the bf16 copy only
+        lr = float(self.param_groups[0]["lr"])
+        counts = [N.lib().sei_sgd_partials(lo, hi, self.grid_cap) for lo, hi in self._ranges]
+        if self.anchor is not None and (self._partials is None or self._partials.numel() < sum(counts)):
+            self._partials = torch.zeros(sum(counts), dtype=torch.float64, device=flat.device)
+        done = 0
+        for (lo, hi), count in zip(self._ranges, counts):
+            N.call("sei_sgd_fused", flat.data_ptr(), grads.data_ptr(), N.ptr(self.anchor), N.ptr(self.coef64), lo, hi,
+                   lr, 1.0, N.ptr(shadow), None if self.anchor is None else self._partials.data_ptr() + 8 * done,
+                   self.grid_cap)
+            done += count
+        if self.anchor is not None:
+            N.call("sei_sgd_penalty_finish", self._partials.data_ptr(), done, self.last_penalty.data_ptr())
+        # bf16 weight shadows must be rebuilt before the next forward (the plain copy just was, if asked)
+        _ops.weights_updated(backbone, plain_shadow_written=shadow is not None)

@@ -9,7 +9,7 @@ arithmetic is exercised by the goldens below except `adjoint_function`, which is
 `torch.autograd.functional.vjp` (flagged "vjp" in the fixture names).
 
 What is written is DATA ONLY: seeded inputs and the outputs the reference produced for them
-(G12 noise2inverse; G13 the in-tree R2R / EI loss; G14 CropPair on batches; G15 the loss layer end to end; G16 CTLikeFilter). The reference cannot travel to the GPU box; these files can.
+(G12 noise2inverse; G13 the in-tree R2R / EI loss; G14 CropPair on batches; G15 the loss layer end to end; G16 CTLikeFilter; G17 WeightsDistanceLoss + SGD). The reference cannot travel to the GPU box; these files can.
 
     python tools/gen_golden.py            # writes tests/golden/*.npz + manifest json
 """
@@ -483,6 +483,57 @@ def gen_ct_like_filter():
         _save(name, **arrs)
 
 
+G17_SHAPES = {"w0": (5, 3, 3, 3), "b0": (1,), "w1": (64, 32, 1, 1), "b1": (65,)}
+
+
+def gen_weights_distance():
+    """G17: src/losses/weights_distance_loss.py (torch only, loaded by path) and torch.optim.SGD on a four-parameter module
+    whose sizes meet every case of the 64-element blocks of the flat bucket: 1 alone in a block, 65 spilling into a
+    second, 135 odd, 2048 aligned. Stored: the anchors (`anchor.*`), the perturbed current values (`param.*`), an external
+    gradient per parameter (`grad.*`), `lr`; the reference's loss at lambd = 1 in float32 and in float64 (`loss32`,
+    `loss64`), its float64 gradients (`f64.penalty_grad.*`) and the float64 parameters after one SGD step on
+    external-plus-penalty gradient (`f64.stepped.*`). Inputs are float32-representable; lr |g'| stays below max |p|."""
+    os.makedirs(OUT, exist_ok=True)
+    wdl = _load_by_path("ref_weights_distance_loss", os.path.join(REF_SRC, "losses", "weights_distance_loss.py"))
+
+    class Four(torch.nn.Module):
+        def __init__(self, values):
+            super().__init__()
+            for name, v in values.items():
+                setattr(self, name, torch.nn.Parameter(v.clone()))
+
+    lr = 1e-2
+    anchors = {n: 0.5 * _randn(sh, 171 + k) for k, (n, sh) in enumerate(G17_SHAPES.items())}
+    current = {n: anchors[n] + 0.1 * _randn(sh, 181 + k) for k, (n, sh) in enumerate(G17_SHAPES.items())}
+    ext = {n: _randn(sh, 191 + k) for k, (n, sh) in enumerate(G17_SHAPES.items())}
+    arrs = {"lr": np.asarray(lr, dtype=np.float64)}
+    for n in G17_SHAPES:
+        arrs[f"anchor.{n}"], arrs[f"param.{n}"], arrs[f"grad.{n}"] = _np(anchors[n]), _np(current[n]), _np(ext[n])
+    loss32 = wdl.WeightsDistanceLoss(pretrained_model=Four(anchors), lambd=1, device="cpu")(Four(current))
+    assert loss32.dtype == torch.float32
+    arrs["loss32"] = _np(loss32)
+    torch.set_default_dtype(torch.float64)          # the reference accumulates into torch.zeros(()): the default dtype
+    try:
+        model = Four({n: v.double() for n, v in current.items()})
+        loss64 = wdl.WeightsDistanceLoss(pretrained_model=Four({n: v.double() for n, v in anchors.items()}), lambd=1,
+                                         device="cpu")(model)
+    finally:
+        torch.set_default_dtype(torch.float32)
+    assert loss64.dtype == torch.float64
+    arrs["loss64"] = _np(loss64)
+    loss64.backward()
+    worst = 0.0
+    for n, prm in model.named_parameters():
+        arrs[f"f64.penalty_grad.{n}"] = _np(prm.grad)
+        prm.grad = prm.grad + ext[n].double()
+        worst = max(worst, float(prm.grad.abs().max()))
+    assert lr * worst <= max(float(v.abs().max()) for v in current.values())
+    torch.optim.SGD(model.parameters(), lr=lr).step()
+    for n, prm in model.named_parameters():
+        arrs[f"f64.stepped.{n}"] = _np(prm)
+    _save("g17_weights_distance", **arrs)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     _install_deepinv_shell()
@@ -858,6 +909,8 @@ if __name__ == "__main__":
         gen_loss_glue()
     elif sys.argv[1:] == ["--only", "g16"]:
         gen_ct_like_filter()
+    elif sys.argv[1:] == ["--only", "g17"]:
+        gen_weights_distance()
     else:
         main()
         gen_noise2inverse()
@@ -865,3 +918,4 @@ if __name__ == "__main__":
         gen_crop()
         gen_loss_glue()
         gen_ct_like_filter()
+        gen_weights_distance()

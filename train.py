@@ -18,6 +18,13 @@ step runs in libsei_hip.so. Differences, all build-side and documented in DESIGN
   * the per-step `.item()` host sync of the reference is replaced by a device-side running mean.
   * `--task invert_a_tomography_like_filter` with the default `--partial_sure` needs `--sure_margin N` (or
     `--no-partial_sure`): the reference has no default margin for this task and stops on an unbound name.
+  * `--fine_tuning` (demo/train.py:95-114, 144-186, 245-264): `--dataset DIR` trains on the measured PNGs of a folder
+    (one random crop per file, kept on the device), the defaults become SGD at 1e-2, `--weights_distance_loss` keeps the
+    weights near the loaded ones and `--fine_tuning_params` steps SwinIR's `conv_last` alone. With `--fused_optimizer`
+    the SGD step and the penalty are one fused kernel (optim.FlatSGD) and the step replays from a hipGraph; with
+    `--no-fused_optimizer` it is the reference's literal sequence (losses/weights_distance_loss.py + torch.optim.SGD).
+    The reference's assertions are ValueErrors raised before anything touches the GPU; `--fine_tuning_params` with the
+    Convolutional architecture, which has no `conv_last`, is one of them (the reference dies in `get_parameter`).
 """
 import csv
 import os
@@ -25,6 +32,7 @@ import random
 import sys
 from argparse import BooleanOptionalAction
 from datetime import datetime
+from os.path import isdir
 
 import numpy as np
 import torch
@@ -37,7 +45,7 @@ import parallel  # noqa: E402
 from datasets import get_dataset  # noqa: E402
 from losses import get_loss  # noqa: E402
 from models import get_model  # noqa: E402
-from optim import FlatAdam  # noqa: E402
+from optim import FlatAdam, FlatSGD  # noqa: E402
 from physics import get_physics  # noqa: E402
 from scheduler import get_lr_scheduler  # noqa: E402
 from settings import DefaultArgParser  # noqa: E402
@@ -103,6 +111,54 @@ def build_parser():
     return parser
 
 
+FINE_TUNING_PARAMS = ["model.model.conv_last.weight", "model.model.conv_last.bias"]       # demo/train.py:180-183
+
+
+def check_fine_tuning_args(args):
+    """The reference's assertions on the fine-tuning flags (demo/train.py:96-97, :179, :246), before any GPU object."""
+    if args.dataset is not None and isdir(args.dataset):
+        if not args.fine_tuning:
+            raise ValueError("Datasets of predictors only are only supported for fine-tuning (--fine_tuning)")
+        if args.method != "proposed":
+            raise ValueError("Fine-tuning is only supported for the proposed method (--method proposed)")
+    if args.fine_tuning_params and not args.fine_tuning:
+        raise ValueError("Fine-tuning parameters are only supported for fine-tuning (--fine_tuning)")
+    if args.weights_distance_loss and not args.fine_tuning:
+        raise ValueError("Weights distance loss is only supported for fine-tuning (--fine_tuning)")
+    if args.fine_tuning_params and args.ProposedModel__architecture != "Transformer":
+        raise ValueError(f"--fine_tuning_params trains {FINE_TUNING_PARAMS[0]} and {FINE_TUNING_PARAMS[1]}: only "
+                         "--ProposedModel__architecture Transformer has a conv_last, not "
+                         f"{args.ProposedModel__architecture}")
+
+
+def _crop_offsets(height, width, size):
+    """torchvision's RandomCrop.get_params: two CPU-generator draws, none when the image is exactly the crop."""
+    if height < size or width < size:
+        raise ValueError(f"Required crop size {(size, size)} is larger than input image size {(height, width)}")
+    if height == size and width == size:
+        return 0, 0
+    i = torch.randint(0, height - size + 1, size=(1,)).item()
+    j = torch.randint(0, width - size + 1, size=(1,)).item()
+    return i, j
+
+
+def measurement_folder(path, crop_size, device):
+    """demo/train.py:98-114: every *.png of a folder as a measurement y in [0, 1] (three channels), one random
+    `crop_size` crop per file drawn at load time, kept on the device; x is a dummy of zeros that the loss never reads
+    (cropped separately, as the reference does: the same draws from the CPU generator)."""
+    from glob import glob
+    from datasets._io import read_image
+    pairs = []
+    for f in glob(os.path.join(path, "*.png")):
+        y = read_image(f).to(device).float() / 255.0
+        y = y[:3, :, :]                                       # discard the alpha channel if it exists
+        _crop_offsets(y.shape[1], y.shape[2], crop_size)      # x's own crop of zeros
+        i, j = _crop_offsets(y.shape[1], y.shape[2], crop_size)
+        y = y[:, i:i + crop_size, j:j + crop_size].contiguous()
+        pairs.append((torch.zeros_like(y), y))
+    return pairs
+
+
 def main(argv=None):
     rank, local_rank, world = parallel.init_from_env()
     seed = 0 + rank                                   # reference: all seeds 0 (single process)
@@ -114,8 +170,7 @@ def main(argv=None):
     if args.device == "cuda" and world > 1:
         args.device = f"cuda:{local_rank % torch.cuda.device_count()}"     # (% only matters for shared-GPU rehearsals)
         torch.cuda.set_device(args.device)
-    if args.fine_tuning or args.fine_tuning_params or args.weights_distance_loss:
-        raise NotImplementedError("fine-tuning options are outside the hot path of this build")
+    check_fine_tuning_args(args)
     crop.FIX_BATCHED_CROP = args.fix_batched_crop
 
     physics = get_physics(args, device=args.device)
@@ -130,8 +185,11 @@ def main(argv=None):
     torch.cuda.manual_seed(seed)                      # decorrelated b / noise / rates / centres per rank
 
     loss = get_loss(args=args, physics=physics)
-    dataset = get_dataset(args=args, purpose="train", physics=physics, device=args.device,
-                          _HOTFIX=(args.task == "sr"))
+    if isdir(args.dataset):
+        dataset = measurement_folder(args.dataset, args.PrepareTrainingPairs__crop_size, args.device)
+    else:
+        dataset = get_dataset(args=args, purpose="train", physics=physics, device=args.device,
+                              _HOTFIX=(args.task == "sr"))
     sampler = None
     if world > 1:
         sampler = torch.utils.data.distributed.DistributedSampler(dataset, shuffle=True, seed=0)
@@ -141,6 +199,8 @@ def main(argv=None):
     if args.device_cache:
         if args.method == "css" or not args.SyntheticDataset__deterministic_measurements:
             raise ValueError("--device_cache needs deterministic measurements (and no css re-degradation)")
+        if isdir(args.dataset):
+            raise ValueError("--device_cache holds (x, y) pairs of a dataset; a folder of measurements is on the device already")
         from datasets import SyntheticPairs
         from datasets.device_cache import DeviceResidentPairs
         if isinstance(dataset, SyntheticPairs):
@@ -154,26 +214,37 @@ def main(argv=None):
             print(f"\nDevice cache: {len(device_cache)} pairs, {device_cache.nbytes() / 2**20:.0f} MiB\n")
 
     epochs = args.epochs if args.epochs is not None else {"urban100": 4000, "ct": 100}.get(args.dataset, 500)
-    lr = args.lr if args.lr is not None else (2e-4 if args.task == "sr" else 1e-4)
-    optimizer_kind = args.optimizer if args.optimizer is not None else "Adam"
+    if args.lr is not None:
+        lr = args.lr
+    elif args.fine_tuning:
+        lr = 1e-2
+    else:
+        lr = 2e-4 if args.task == "sr" else 1e-4
+    optimizer_kind = args.optimizer if args.optimizer is not None else ("SGD" if args.fine_tuning else "Adam")
     if rank == 0:
         print(f"\nSelected learning rate: {lr:e}\n")
         print(f"\nSelected optimizer: {optimizer_kind}\n")
 
     from models import _ops as model_ops
     model_ops.set_compute_dtype(args.compute_dtype)
-    fused_adam = optimizer_kind == "Adam" and args.fused_optimizer
+    # FlatAdam steps the whole bucket and knows no penalty: with either fine-tuning option Adam is torch's own
+    fused_adam = optimizer_kind == "Adam" and args.fused_optimizer and not (args.fine_tuning_params
+                                                                            or args.weights_distance_loss)
     if args.grad_comm_dtype == "bf16" and not fused_adam:
         raise ValueError("--grad_comm_dtype bf16 needs the fused Adam (it reads the bf16 bucket directly)")
     comm_dtype = torch.bfloat16 if args.grad_comm_dtype == "bf16" else torch.float32
     reducer = parallel.FlatGradientReducer(backbone.flat_grads, comm_dtype=comm_dtype,
                                            mode=args.grad_comm_mode) if parallel.exchange_active() else None
-    if optimizer_kind == "Adam" and args.fused_optimizer:
+    only = FINE_TUNING_PARAMS if args.fine_tuning_params else None
+    params = model.parameters() if only is None else [model.get_parameter(key) for key in only]
+    if fused_adam:
         optimizer = FlatAdam(model, lr=lr, betas=(0.9, args.optimizer_beta2), reducer=reducer)
     elif optimizer_kind == "Adam":
-        optimizer = torch.optim.Adam(model.parameters(), lr=lr, betas=(0.9, args.optimizer_beta2))
+        optimizer = torch.optim.Adam(params, lr=lr, betas=(0.9, args.optimizer_beta2))
+    elif optimizer_kind == "SGD" and args.fused_optimizer:
+        optimizer = FlatSGD(model, lr=lr, anchor=args.weights_distance_loss or None, lambd=1.0, only=only)
     elif optimizer_kind == "SGD":
-        optimizer = torch.optim.SGD(model.parameters(), lr=lr)
+        optimizer = torch.optim.SGD(params, lr=lr)
     else:
         raise ValueError(f"Unknown optimizer: {optimizer_kind}")
     scheduler = get_lr_scheduler(optimizer=optimizer, epochs=epochs, lr_scheduler_kind=args.lr_scheduler_kind)
@@ -200,6 +271,8 @@ def main(argv=None):
         assert args.lr is not None
         for group in optimizer.param_groups:
             group["lr"] = args.lr
+        if isinstance(optimizer, FlatSGD) and optimizer.anchor is not None:
+            optimizer.anchor.copy_(backbone.flat_params)      # as upstream: the penalty's anchor is the resumed model
 
     checkpoints_dir = f"{args.out_dir}/checkpoints"
 
@@ -217,6 +290,13 @@ def main(argv=None):
         save_training_state(epoch=0, model=model, optimizer=optimizer, scheduler=scheduler,
                             state_path=checkpoint_name(0))
 
+    # the reference's literal penalty (a deepcopy of the model as it stands here, added to the loss before backward()):
+    # every optimizer but FlatSGD, whose kernel applies the same penalty and leaves its value in `last_penalty`
+    weights_distance = None
+    if args.weights_distance_loss and not isinstance(optimizer, FlatSGD):
+        from losses.weights_distance_loss import WeightsDistanceLoss
+        weights_distance = WeightsDistanceLoss(pretrained_model=model, lambd=1, device=args.device)
+
     graphed, early_event = None, None
     trace_step_kind = rank == 0 and os.environ.get("SEI_TRACE_STEP_KIND") == "1"
     for epoch in range(epochs):
@@ -228,7 +308,7 @@ def main(argv=None):
         for x, y in batches:
             x, y = x.to(args.device), y.to(args.device)
             used_graph = False
-            can_graph = (args.hip_graph and isinstance(optimizer, FlatAdam) and graphs.can_capture(loss)
+            can_graph = (args.hip_graph and isinstance(optimizer, (FlatAdam, FlatSGD)) and graphs.can_capture(loss)
                          and y.shape[0] == args.batch_size)
             if can_graph:
                 if graphed is None:                   # capture once; short last batches run eagerly
@@ -237,7 +317,8 @@ def main(argv=None):
                     graphed = GraphedLossStep(loss, model, optimizer,
                                               (args.batch_size, y.shape[1], args.Loss__crop_size, args.Loss__crop_size),
                                               early_release=early,
-                                              fuse_optimizer=reducer is None and args.fuse_optimizer_step)
+                                              fuse_optimizer=(reducer is None and args.fuse_optimizer_step
+                                                              and isinstance(optimizer, FlatAdam)))
                     if early and graphed.early_grads is not None:
                         early_event = graphed.early_grads[0]
                         # (a capture after sharded optimizer steps -- the first batches were short -- changes which
@@ -250,6 +331,8 @@ def main(argv=None):
             else:
                 optimizer.zero_grad()
                 training_loss = loss(x=x, y=y, model=model)
+                if weights_distance is not None:
+                    training_loss = training_loss + weights_distance(model)
                 training_loss.backward()
             if trace_step_kind:                       # tests: which launch path the first step took
                 print("step kind: hipGraph replay" if used_graph else "step kind: eager")
@@ -262,6 +345,8 @@ def main(argv=None):
                     backbone.flat_grads /= world
             optimizer.step()
             loss_sum += training_loss.detach()
+            if isinstance(optimizer, FlatSGD):
+                loss_sum += optimizer.last_penalty            # the logged loss includes the penalty, as upstream
             steps += 1
             if args.max_steps is not None and steps >= args.max_steps:
                 break
