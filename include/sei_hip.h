@@ -226,6 +226,39 @@ int sei_luma_sqerr(const float *a, const float *b, size_t npix, float *out1, flo
 int sei_ssim_luma(const float *a, const float *b, int batch, int H, int W, float *out, float *work, void *stream);
 size_t sei_ssim_luma_work_floats(int batch, int H, int W);
 
+/* LPIPS v0.1 on AlexNet features (csrc/lpips_kernels.hip; reference src/metrics.py: pyiqa.create_metric("lpips")), float32.
+ * For an H x W RGB image in [0, 1] (H, W >= 31: below that the second pool has nothing to work on):
+ *   v = ((2 x - 1) - shift) / scale per channel, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450);
+ *   layer 0: relu(conv(v; 3 -> 64, k 11, stride 4, zero pad 2)), then maxpool(3, stride 2, floor mode, no padding);
+ *   layer 1: relu(conv(64 -> 192, k 5, pad 2)), then the same pool;  layers 2, 3, 4: relu(conv(k 3, pad 1)) with
+ *   192 -> 384, 384 -> 256, 256 -> 256 channels. The zero padding of layer 0 pads v, not x: a padded tap contributes 0.
+ *   d_l = mean over pixels of sum_c lin_l[c] (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2 for the two images' maps of
+ *   layer l, |.| the norm over the channels of the pixel; LPIPS = d_0 + d_1 + d_2 + d_3 + d_4.
+ * Every entry takes the IMAGE extents H, W and the layer index and derives its own extents from them. Maps are
+ * channels-last, [image][pixel][C], 16-byte aligned.
+ *   sei_lpips_conv_relu: layer 0 reads `n` planar (3, H, W) images, 4-byte aligned, the first `split` of them from x and
+ *     the rest from x2 (NULL with split == n), and applies the input scaling on load; layers 1 .. 4 read the n maps at x (the
+ *     POOLED map for layers 1 and 2; x2 and split are ignored). w: the weight repacked to [Cout][K], 16-byte aligned: layer 0
+ *     K = 384 = torch's (64, 3 * 11 * 11) rows padded with zeros; layers 1 .. 4 K = k * k * Cin in (ky, kx, ci) order (torch's
+ *     weight.permute(0, 2, 3, 1)). bias [Cout]. y: n maps [Hout * Wout][Cout]. An implicit GEMM on the exact-float32 matrix
+ *     instructions; the k-ordered chain is closed every 256 k.
+ *   sei_lpips_maxpool: the pool behind layer 0 or 1, x = that layer's n maps.
+ *   sei_lpips_layer_dist: out[i] = d_layer of fa's and fb's i-th maps (accumulate = 0) or out[i] += d_layer (accumulate != 0:
+ *     called for layers 0 .. 4 in order it leaves the LPIPS). lin [C], non-negative. `work` holds 1024 floats per image, the
+ *     per-workgroup partial sums, which one workgroup per image adds in index order in double.
+ *   sei_lpips_work_floats: the floats one evaluation of `batch` pairs needs for everything between the images and the result
+ *     (the 2 * batch maps of layer 0, its pooled maps, layer 1, its pooled maps, layers 2, 3, 4, in that order, then the
+ *     partial sums); 0 = arguments refused.
+ * SEI_ERR_BAD_ARG on NULL or misaligned pointers, non-positive counts, a layer outside its range and extents below 31 (or
+ * above 32768, or more than 2^28 pixels); nothing is launched then. Deterministic: no atomics, and the grids depend on the
+ * extents only, so an image's result does not depend on the batch it is in. */
+int sei_lpips_conv_relu(const float *x, const float *x2, int split, const float *w, const float *bias, float *y, int layer,
+                        int n, int H, int W, void *stream);
+int sei_lpips_maxpool(const float *x, float *y, int layer, int n, int H, int W, void *stream);
+int sei_lpips_layer_dist(const float *fa, const float *fb, const float *lin, int layer, int batch, int H, int W, float *out,
+                         int accumulate, float *work, void *stream);
+size_t sei_lpips_work_floats(int batch, int H, int W);
+
 /* ---------------------------------------------------------------------------------------------
  * Baselines of the evaluation driver (csrc/tv_kernels.hip; reference src/models/tv.py).
  *

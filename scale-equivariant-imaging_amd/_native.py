@@ -52,6 +52,9 @@ SIGNATURES = {
     "sei_mse_loss": [_P, _P, _Z, _F, _F, _P, _P, _P, _P],
     "sei_luma_sqerr": [_P, _P, _Z, _P, _P, _P],
     "sei_ssim_luma": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "sei_lpips_conv_relu": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
+    "sei_lpips_maxpool": [_P, _P, _I, _I, _I, _I, _P],
+    "sei_lpips_layer_dist": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P],
     "sei_tv_prox": [_P, _P, _P, _I, _I, _I, _F, _I, _P, _P],
     "sei_tv_prox_ex": [_P, _P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P],
     "sei_dip_stage_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P],
@@ -185,6 +188,7 @@ TRANSPOSE_MAX_JOBS = 16
 SIZE_QUERIES = {
     "sei_proposed_draws_max_numel": [],
     "sei_ssim_luma_work_floats": [_I, _I, _I],
+    "sei_lpips_work_floats": [_I, _I, _I],
     "sei_tv_prox_work_floats": [_I, _I, _I],
     "sei_dip_work_floats": [_I, _I, _I, _I],
     "sei_dwconv7_bwd_weight_workspace": [_I, _I, _I, _I],

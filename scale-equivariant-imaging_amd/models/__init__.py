@@ -13,7 +13,8 @@ either) and "DeepImagePrior" (models/dip.py: deepinv's untrained ConvDecoder res
 the fused sei_dip_* kernels; parity with deepinv unpinned, the float64 restatement in tests/test_dip_baseline_gpu.py is the
 pinned truth; --dip_iterations, with the reference's defaults for deblurring and sr). The other test-time baselines (PnP,
 BM3D, DiffPIR, DPS) need pretrained networks or a package that is not here; they raise a clear error instead of silently
-running something else.
+running something else. (The one pretrained network that IS rebuilt sits outside this factory: the AlexNet features of the
+LPIPS metric, metrics.LPIPS, five convolutions whose two small published weight files the user names to test.py.)
 """
 from os import environ
 

@@ -14,8 +14,10 @@ backbone), `--r2r`, and the classical baseline `--model_kind TV --tv_lambd L [--
 gradient on sei_tv_prox; without --tv_lambd it raises, the reference has no default either) and `--model_kind DeepImagePrior
 [--dip_iterations N]` (models/dip.py: an untrained decoder fitted to every measurement by Adam on the sei_dip_* kernels; its
 forward needs no autograd, so the reference's `dip` switch around no_grad has nothing to do here). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
-`SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. LPIPS always prints nan (pyiqa and its
-pretrained weights are not rebuilt). Out of scope and refused: PnP / BM3D / DiffPIR / DPS baselines (pretrained
+`SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. `--lpips_backbone FILE --lpips_linear FILE`
+(build-side addition; both or neither) name a torchvision AlexNet state dict and the LPIPS v0.1 `alex` linear layers: the
+`LPIPS:`, `LPIPS std:` and `LIPS:` fields then carry metrics.lpips_fn's values (the sei_lpips_* kernels); without them they
+print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: PnP / BM3D / DiffPIR / DPS baselines (pretrained
 networks or the bm3d package).
 """
 import os
@@ -30,7 +32,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "sca
 
 from datasets import get_dataset  # noqa: E402
 from datasets._io import read_image  # noqa: E402
-from metrics import compute_metrics  # noqa: E402
+from metrics import LPIPS, compute_metrics  # noqa: E402
 from models import get_model  # noqa: E402
 from physics import get_physics  # noqa: E402
 from settings import DefaultArgParser  # noqa: E402
@@ -57,7 +59,19 @@ def build_parser():
     flag("--memoize_gt", action=BooleanOptionalAction, default=False)
     flag("--compute_dtype", choices=["f32", "bf16", "bf16x3"], default="f32")          # build-side addition
     flag("--ssim", action="store_true")                                                  # build-side addition
+    flag("--lpips_backbone", type=str, default=None, metavar="FILE")                     # build-side addition
+    flag("--lpips_linear", type=str, default=None, metavar="FILE")                       # build-side addition
     return parser
+
+
+def parse_args(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if (args.lpips_backbone is None) != (args.lpips_linear is None):
+        given, other = ("--lpips_backbone", "--lpips_linear") if args.lpips_linear is None else \
+            ("--lpips_linear", "--lpips_backbone")
+        parser.error(f"{given} needs {other} as well: LPIPS takes both weight files or neither")
+    return args
 
 
 def quantize_and_clamp(im):
@@ -80,7 +94,7 @@ def save_image(im, path):
 def main(argv=None):
     torch.manual_seed(0)
     np.random.seed(0)
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     from models import _ops as model_ops
     model_ops.set_compute_dtype(args.compute_dtype)
 
@@ -90,6 +104,10 @@ def main(argv=None):
     model.eval()
     if args.weights is not None:
         model.load_weights(get_weights(args.weights, args.device))
+
+    lpips_net = None
+    if args.lpips_backbone is not None:
+        lpips_net = LPIPS.from_files(args.lpips_backbone, args.lpips_linear, device=args.device)
 
     basename_table = {}
     if isdir(args.dataset):                                   # a folder of measurements, no ground truth
@@ -138,7 +156,8 @@ def main(argv=None):
         y = quantize_and_clamp(y)
         x_hat = quantize_and_clamp(x_hat)
         if x is not None:
-            psnr_val, ssim_val, lpips_val = compute_metrics(x.squeeze(0), x_hat.squeeze(0), ssim=args.ssim)
+            psnr_val, ssim_val, lpips_val = compute_metrics(x.squeeze(0), x_hat.squeeze(0), ssim=args.ssim,
+                                                            lpips=lpips_net)
             psnr_list.append(psnr_val)
             ssim_list.append(ssim_val)
             lpips_list.append(lpips_val)
