@@ -433,8 +433,10 @@ int sei_ln_bwd_res(const float *x, const float *gamma, const float *mean, const 
  * gradients of a whole backward pass (reference: the autograd of src/models/convolutional.py:21-39 accumulates each of
  * them into its parameter's .grad; here a reducing kernel leaves per-workgroup partial sums and a fold adds them up in a
  * fixed order). A job is ONE destination and the partial-sum arrays of up to three launches that add to it (the model
- * calls of a step that share the parameter), folded one after the other exactly as their own fold launches would have:
- * bit-identical, in 1 launch instead of ~50 (U-Net step) / ~146 (SwinIR step).
+ * calls of a step that share the parameter), folded one after the other into the running value. The entry points that
+ * are handed their destinations fold with the same device routine, one job per launch (the order of the additions is
+ * stated once, at fold_entries in csrc/reduce_kernels.hip): bit-identical, in 1 launch instead of ~50 (U-Net step) / ~146
+ * (SwinIR step).
  *   SEI_FOLD_SPLIT:   part[s]: [groups[s]][ncol]; entry e adds to a[e] (e < split), b[e - split] (e < 2 split) or
  *                     c[e - 2 split] (c may be NULL: dropped) -- sei_ln_bwd (ncol = 2 C, split = C),
  *                     sei_rowgemm_lnbwd_bf16 (ncol = 3 C), a plain column sum (ncol = split);

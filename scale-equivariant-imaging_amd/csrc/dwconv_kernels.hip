@@ -2,7 +2,7 @@
 // (reference: src/models/convolutional.py:36-38,46 -- nn.Conv2d(C, C, 7, padding=3, groups=C)).
 //
 //   sei_dwconv7_fwd         forward; with flip=1 and a residual it is the data gradient of the block
-//   sei_dwconv7_bwd_weight  weight + bias gradient, two deterministic stages (partials, then a fold)
+//   sei_dwconv7_bwd_weight  weight + bias gradient, two deterministic stages (partials, then the fold of reduce_kernels.hip)
 //
 // Every level of the default network moves the same 18.9 MB per tensor (C quadruples as H*W quarters), so
 // all three regimes below matter equally:
@@ -378,42 +378,6 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv7_whole_kernel(
     }
 }
 
-// stage 2 of the weight gradient: gw[c][t] += sum_p part[p][t][c]; gbias[c] += sum_p part[p][49][c].
-// A workgroup owns FIN_E consecutive (t, c) entries and splits the partials over FIN_S interleaved slices
-// (many short chains of independent loads), then folds the slices through LDS in a fixed order
-// (bitwise reproducible; no atomics).
-constexpr int FIN_E = 16, FIN_S = 16;
-__global__ __launch_bounds__(FIN_E * FIN_S) void dwconv7_wgrad_finish_kernel(const float *__restrict__ part,
-                                                                             int nparts, int C,
-                                                                             float *__restrict__ gw,
-                                                                             float *__restrict__ gbias) {
-    __shared__ float red[FIN_S][FIN_E];
-    const int el = threadIdx.x % FIN_E, slice = threadIdx.x / FIN_E;
-    const int e = blockIdx.x * FIN_E + el;               // e = t*C + c
-    const size_t stride = (size_t)50 * C;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (e < 50 * C) {
-        int p = slice;
-        for (; p + 3 * FIN_S < nparts; p += 4 * FIN_S) {
-            s0 += part[(size_t)p * stride + e];
-            s1 += part[(size_t)(p + FIN_S) * stride + e];
-            s2 += part[(size_t)(p + 2 * FIN_S) * stride + e];
-            s3 += part[(size_t)(p + 3 * FIN_S) * stride + e];
-        }
-        for (; p < nparts; p += FIN_S) s0 += part[(size_t)p * stride + e];
-    }
-    red[slice][el] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (slice == 0 && e < 50 * C) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < FIN_S; ++k) s += red[k][el];
-        const int t = e / C, c = e - t * C;
-        if (t < 49) gw[(size_t)c * 49 + t] += s;
-        else if (gbias) gbias[c] += s;
-    }
-}
-
 enum DwPath { DW_GENERIC, DW_TILED, DW_WHOLE3, DW_WHOLE6 };
 // seg: the `seg` argument of the _ex entry points: 0 = choose by shape, 1..64 = the generic kernels with that many
 // output columns per worker segment (tests compare the paths; tools/exp_dwseg.py times them)
@@ -452,7 +416,7 @@ inline DwWgradPlan dw_wgrad_plan(int B, int H, int W, int C, int seg) {
         p.nparts = p.gx;
     } else if (p.path == DW_WHOLE3 || p.path == DW_WHOLE6) {
         p.gx = (unsigned)sei_ceil_div(C, DW_THREADS);
-        // image groups = partial sets.  Each set is 50 x C floats written here and read back by the finish kernel, against
+        // image groups = partial sets.  Each set is 50 x C floats written here and read back by the fold, against
         // H x W x C floats of x and of gy per image: keep the partials below about half of the input bytes, but at least
         // 8 groups (and ~256 workgroups) so the chip still has waves to hide the strided image loads behind.
         size_t want = (size_t)B * H * W / 64;
@@ -572,11 +536,8 @@ extern "C" int sei_dwconv7_bwd_weight_ex(const float *x, const float *gy, float 
         hipLaunchKernelGGL(dwconv7_kernel<true>, dim3(p.gx, p.gy), dim3(DW_THREADS), lds, s, x, nof, nof, nof, 0.f, nom,
                            gy, work, B, H, W, C, 0, p.Cc, p.nseg, (int)p.total, p.seg);
     }
-    // stage 2: fold the partials into the running gradient
-    if (gw)
-        hipLaunchKernelGGL(dwconv7_wgrad_finish_kernel, dim3((unsigned)sei_ceil_div((size_t)50 * C, FIN_E)),
-                       dim3(FIN_E * FIN_S), 0, s,
-                       (const float *)work, (int)p.nparts, C, gw, gbias);
+    // stage 2: fold the partials into the running gradient -- gw[c][t] += sum_p part[p][t][c], gbias[c] += sum_p part[p][49][c]
+    if (gw) return sei_fold_now(sei_fold_job(SEI_FOLD_DWCONV7, work, (int)p.nparts, 50 * C, C, gw, gbias, nullptr), s);
     return sei_launch_status();
 }
 

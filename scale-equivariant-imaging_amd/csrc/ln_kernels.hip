@@ -4,7 +4,7 @@
 //
 // HBM-bound streaming kernels: channels are the contiguous axis, so lanes map to channels and every global access is a
 // coalesced 256-B wave row. The parameter gradients of the vectorised shapes are per-workgroup partial rows, folded in a
-// fixed order by ln_bwd_fold_kernel or sei_fold_many (reduce_kernels.hip); the legacy shapes add with float atomics after
+// fixed order by sei_fold_now or sei_fold_many (reduce_kernels.hip); the legacy shapes add with float atomics after
 // an in-block LDS reduction (gradients are accumulators by contract).
 #include "sei_common.h"
 
@@ -219,8 +219,8 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_wide_kernel(
 }
 
 // ---- LayerNorm backward, vectorised (C % 4 == 0) -----------------------------------------------------------
-// Parameter gradients are written as per-workgroup partial rows into a workspace and folded by
-// ln_bwd_fold_kernel in a fixed order (no atomics, bitwise reproducible).
+// Parameter gradients are written as per-workgroup partial rows into a workspace and folded in the fixed order of
+// reduce_kernels.hip (no atomics, bitwise reproducible).
 //
 // narrow rows (C = 4*G*NV, G a power of two <= 64): G lanes own one row, NV float4 each; 256/G rows per sweep.
 template <int G, int NV>
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_vec_kernel(
 // wide rows in ONE pass (C = 1024 NV, NV <= 8; round 5): a workgroup takes whole rows -- a thread owns NV float4 of the row,
 // 1 KiB apart, so x and gy are read ONCE (the two-pass form below reads both twice: 565 MB per 113-MB tensor where this one
 // moves 340 MB + the partials) --, folds the row's two sums over its four waves through LDS, writes gx, and keeps the
-// parameter-gradient partials of ITS rows in registers: part[workgroup][2 C] for sei_fold_many / ln_bwd_fold_kernel.
+// parameter-gradient partials of ITS rows in registers: part[workgroup][2 C] for sei_fold_many / sei_fold_now.
 // The next row's loads are issued before the current row's sums are exchanged.
 template <int NV>
 __global__ __launch_bounds__(LN_THREADS) void ln_bwd_row_kernel(
@@ -460,36 +460,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_cols_kernel(
     float *out = part + (size_t)blockIdx.y * 2 * C;
     *reinterpret_cast<float4 *>(out + c) = dg;
     *reinterpret_cast<float4 *>(out + C + c) = db;
-}
-
-// fold: ggamma[c] += sum_p part[p][c]; gbeta[c] += sum_p part[p][C + c]   (16 entries x 16 slices per workgroup)
-__global__ __launch_bounds__(256) void ln_bwd_fold_kernel(const float *__restrict__ part, int nparts, int C,
-                                                          float *__restrict__ ggamma,
-                                                          float *__restrict__ gbeta) {
-    __shared__ float red[16][16];
-    const int el = threadIdx.x & 15, slice = threadIdx.x >> 4;
-    const int e = blockIdx.x * 16 + el;
-    const size_t stride = (size_t)2 * C;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (e < 2 * C) {
-        int p = slice;
-        for (; p + 48 < nparts; p += 64) {
-            s0 += part[(size_t)p * stride + e];
-            s1 += part[(size_t)(p + 16) * stride + e];
-            s2 += part[(size_t)(p + 32) * stride + e];
-            s3 += part[(size_t)(p + 48) * stride + e];
-        }
-        for (; p < nparts; p += 16) s0 += part[(size_t)p * stride + e];
-    }
-    red[slice][el] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (slice == 0 && e < 2 * C) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s += red[k][el];
-        if (e < C) ggamma[e] += s;
-        else gbeta[e - C] += s;
-    }
 }
 
 template <int G>
@@ -668,9 +638,7 @@ extern "C" int sei_ln_bwd_res(const float *x, const float *gamma, const float *m
             hipLaunchKernelGGL(ln_bwd_cols_kernel, dim3(p.col_blocks, p.chunks), dim3(LN_THREADS), 0, s, x, gamma,
                                mean, rstd, gy, (const float2 *)stats, res, gx, part, rows, C, p.rows_per_chunk);
         }
-        if (ggamma)
-            hipLaunchKernelGGL(ln_bwd_fold_kernel, dim3((unsigned)sei_ceil_div((size_t)2 * C, 16)), dim3(256), 0, s,
-                               (const float *)part, (int)p.nparts, C, ggamma, gbeta);
+        if (ggamma) return sei_fold_now(sei_fold_job(SEI_FOLD_SPLIT, part, (int)p.nparts, 2 * C, C, ggamma, gbeta, nullptr), s);
         return sei_launch_status();
     }
     // legacy shapes (C not a multiple of 4, or not 4 * 2^k below 512): scalar lanes, float atomics

@@ -1,7 +1,8 @@
 // Reductions that the backward passes share, gfx950, float32.
 //
 //   sei_colsum_f32 / _weighted_f32 : bias gradients of the 1x1 convolutions (float atomics after an in-block LDS reduction)
-//   sei_fold_many                  : the deferred folds of the depthwise, LayerNorm, cast and conv3x3 weight gradients
+//   sei_fold_many / sei_fold_now   : the second stage of the depthwise, LayerNorm, cast and conv3x3 reductions -- the fold
+//                                    of per-workgroup partial sums, deferred (a job table) or at once (one job)
 #include "sei_common.h"
 
 namespace {
@@ -116,11 +117,13 @@ extern "C" int sei_colsum_weighted_f32(const float *X, const float *row_weight, 
 
 namespace {
 
-// sei_fold_many: the folds of MANY reducing kernels in one launch (the LayerNorm / depthwise weight gradients of a whole
-// backward pass: 34 + 18 launches of ~5 us per U-Net step, ~146 per SwinIR step). A job is one destination with up to
-// three partial-sum arrays (the model calls of the step that share the parameter), folded one after the other into the
-// running value exactly as the separate launches did: same slices, same order, bit-identical. A workgroup owns 64
-// consecutive entries of one job and finds it by walking the job table in the kernel arguments.
+// The second stage of every two-stage reduction of the backward passes: a reducing kernel leaves per-workgroup partial sums
+// part[groups][ncol] and a fold adds them to the running gradient in a fixed order, without atomics (bit-reproducible).
+// A job (SeiFoldJob, include/sei_hip.h) is one destination with up to three partial-sum arrays (the model calls of a step
+// that share the parameter). fold_entries below is THE order; two kernels run it:
+//   fold_one_kernel  (sei_fold_now, internal): one job, folded where the reducing entry point was handed its destinations
+//   fold_many_kernel (sei_fold_many):          a table of jobs in one launch (34 + 18 folds per U-Net step, ~146 per SwinIR
+//                                              step); a workgroup finds its job by walking the table in the kernel arguments
 struct FoldManyArgs {
     SeiFoldJob job[SEI_FOLD_MAX_JOBS];
     int njobs;
@@ -144,6 +147,61 @@ __device__ __forceinline__ float *fold_dst(const SeiFoldJob &J, int e) {
     }                                                            // a | b | c, `split` entries each (c may be absent)
     return e < J.split ? J.a + e : e < 2 * J.split ? J.b + (e - J.split) : (J.c ? J.c + (e - 2 * J.split) : nullptr);
 }
+
+// THE ORDER OF THE FOLD (oracle/fold_order.py is its numpy model; tests/test_fold_order_gpu.py holds every entry point that
+// folds to it, bit for bit). A workgroup of FOLD_SLICES * E threads owns the E consecutive entries from `first` on; lane
+// `el` of slice `k` sums the groups k, k + 16, k + 32, ... of its entry:
+//   * four independent chains while four groups are left, p = k; p + 48 < groups; p += 64:  s_j += part[p + 16 j]
+//   * the tail, p < groups; p += 16, into chain 0
+//   * the chains pair up: (s0 + s1) + (s2 + s3)
+//   * the 16 slices meet in LDS and are added in slice order, from 0.f
+//   * the running value takes the segments one by one: read from the destination (fold_dst) before the first, written
+//     back after the last -- dst + total_0 + total_1 + total_2, as one launch per segment would leave it
+// -ffp-contract=off, no fast-math: these are exactly the float32 additions made.
+template <int E>
+__device__ __forceinline__ void fold_entries(const SeiFoldJob &J, int first, float *red /* LDS [FOLD_SLICES][E] */) {
+    const int el = threadIdx.x % E, slice = threadIdx.x / E;
+    const int e = first + el, ncol = J.ncol;
+    float total = 0.f;
+    for (int sg = 0; sg < J.nseg; ++sg) {
+        const float *part = J.part[sg];
+        const int groups = J.groups[sg];
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        if (e < ncol) {
+            int p = slice;
+            for (; p + 48 < groups; p += 64) {
+                s0 += part[(size_t)p * ncol + e];
+                s1 += part[(size_t)(p + 16) * ncol + e];
+                s2 += part[(size_t)(p + 32) * ncol + e];
+                s3 += part[(size_t)(p + 48) * ncol + e];
+            }
+            for (; p < groups; p += 16) s0 += part[(size_t)p * ncol + e];
+        }
+        if (sg > 0) __syncthreads();                             // (the last segment's read of red)
+        red[slice * E + el] = (s0 + s1) + (s2 + s3);
+        __syncthreads();
+        if (slice == 0 && e < ncol) {
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < FOLD_SLICES; ++k) s += red[k * E + el];
+            float *dst = fold_dst(J, e);
+            if (dst) {
+                if (sg == 0) total = *dst;
+                total += s;
+                if (sg == J.nseg - 1) *dst = total;
+            }
+        }
+    }
+}
+
+// one job, 16 entries x 16 slices per workgroup: many short chains of independent loads for the few hundred entries of one
+// gradient (64 entries per workgroup, four slices of 256-512 DEPENDENT loads each, took 64 us per fold)
+constexpr int FOLD_ONE_E = 16;
+__global__ __launch_bounds__(FOLD_SLICES * FOLD_ONE_E) void fold_one_kernel(SeiFoldJob J) {
+    __shared__ float red[FOLD_SLICES * FOLD_ONE_E];
+    fold_entries<FOLD_ONE_E>(J, (int)blockIdx.x * FOLD_ONE_E, red);
+}
+
 __global__ __launch_bounds__(FOLD_SLICES * FOLD_LANES) void fold_many_kernel(FoldManyArgs g) {
     __shared__ __attribute__((aligned(16))) float red[FOLD_SLICES][4 * FOLD_LANES * FOLD_NQ];
     int j = 0, first = 0;
@@ -227,40 +285,28 @@ __global__ __launch_bounds__(FOLD_SLICES * FOLD_LANES) void fold_many_kernel(Fol
         }
         return;
     }
-    const int e = ((int)blockIdx.x - first) * FOLD_LANES + el;
-    float total = 0.f;
-    for (int sg = 0; sg < J.nseg; ++sg) {
-        const float *part = J.part[sg];
-        const int groups = J.groups[sg];
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        if (e < ncol) {
-            int p = slice;
-            for (; p + 48 < groups; p += 64) {
-                s0 += part[(size_t)p * ncol + e];
-                s1 += part[(size_t)(p + 16) * ncol + e];
-                s2 += part[(size_t)(p + 32) * ncol + e];
-                s3 += part[(size_t)(p + 48) * ncol + e];
-            }
-            for (; p < groups; p += 16) s0 += part[(size_t)p * ncol + e];
-        }
-        __syncthreads();                                         // (the last segment's read of red)
-        red[slice][el] = (s0 + s1) + (s2 + s3);
-        __syncthreads();
-        if (slice == 0 && e < ncol) {
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < FOLD_SLICES; ++k) s += red[k][el];
-            float *dst = fold_dst(J, e);
-            if (dst) {
-                if (sg == 0) total = *dst;
-                total += s;
-                if (sg == J.nseg - 1) *dst = total;
-            }
-        }
-    }
+    fold_entries<FOLD_LANES>(J, ((int)blockIdx.x - first) * FOLD_LANES, &red[0][0]);   // one entry per lane: THE order as written
 }
 
 }  // namespace
+
+namespace {
+int fold_job_check(const SeiFoldJob &J) {
+    SEI_REQUIRE(J.a && J.ncol > 0 && J.split > 0 && J.nseg >= 1 && J.nseg <= 3);
+    SEI_REQUIRE(J.kind == SEI_FOLD_SPLIT || J.kind == SEI_FOLD_DWCONV7);
+    if (J.kind == SEI_FOLD_DWCONV7) SEI_REQUIRE(J.ncol == 50 * J.split);
+    else SEI_REQUIRE(J.ncol <= 3 * J.split && (J.ncol <= J.split || J.b));
+    for (int sg = 0; sg < J.nseg; ++sg) SEI_REQUIRE(J.part[sg] && J.groups[sg] > 0);
+    return 0;
+}
+}  // namespace
+
+int sei_fold_now(const SeiFoldJob &job, hipStream_t s) {
+    if (const int rc = fold_job_check(job)) return rc;
+    hipLaunchKernelGGL(fold_one_kernel, dim3((unsigned)sei_ceil_div((size_t)job.ncol, FOLD_ONE_E)),
+                       dim3(FOLD_SLICES * FOLD_ONE_E), 0, s, job);
+    return sei_launch_status();
+}
 
 extern "C" int sei_fold_many(const SeiFoldJob *jobs, int njobs, void *stream) {
     SEI_REQUIRE(jobs && njobs > 0 && njobs <= SEI_FOLD_MAX_JOBS);
@@ -268,11 +314,7 @@ extern "C" int sei_fold_many(const SeiFoldJob *jobs, int njobs, void *stream) {
     size_t wgs = 0;
     for (int j = 0; j < njobs; ++j) {
         const SeiFoldJob &J = jobs[j];
-        SEI_REQUIRE(J.a && J.ncol > 0 && J.split > 0 && J.nseg >= 1 && J.nseg <= 3);
-        SEI_REQUIRE(J.kind == SEI_FOLD_SPLIT || J.kind == SEI_FOLD_DWCONV7);
-        if (J.kind == SEI_FOLD_DWCONV7) SEI_REQUIRE(J.ncol == 50 * J.split);
-        else SEI_REQUIRE(J.ncol <= 3 * J.split && (J.ncol <= J.split || J.b));
-        for (int sg = 0; sg < J.nseg; ++sg) SEI_REQUIRE(J.part[sg] && J.groups[sg] > 0);
+        if (const int rc = fold_job_check(J)) return rc;
         for (int k = 0; k < j; ++k) SEI_REQUIRE(jobs[k].a != J.a);      // one job per destination: no two workgroups add to one address
         g.job[j] = J;
         bool vec = (J.ncol & 3) == 0;                           // as fold_vec4 in the kernel

@@ -150,5 +150,14 @@ int sei_dwconv7_ln_fused_launch(const float *x, const float *w, const float *bia
                                 const float *beta, float *h1, void *h2, int out16, float *mean, float *rstd, int B, int H,
                                 int W, int C, float eps, hipStream_t s);
 
-// swin_bf16_kernels.hip: out[c] += sum over groups of part[group][..][c] (internal linkage between translation units)
-int sei_fold_partials3(const float *part, int groups, int C, float *a, float *b, float *c3, hipStream_t s);
+// reduce_kernels.hip: the fold of ONE job in a launch of its own, for the entry points that were handed their destinations
+// (the order of the additions: fold_entries there; shared between translation units, not exported: no part of the ABI)
+__attribute__((visibility("hidden"))) int sei_fold_now(const SeiFoldJob &job, hipStream_t s);
+// the job of one partial-sum array part[groups][ncol] (destinations: SEI_FOLD_* in include/sei_hip.h)
+static inline SeiFoldJob sei_fold_job(int kind, const float *part, int groups, int ncol, int split, float *a, float *b,
+                                      float *c) {
+    SeiFoldJob J{};
+    J.a = a; J.b = b; J.c = c; J.ncol = ncol; J.split = split; J.kind = kind; J.nseg = 1;
+    J.part[0] = part; J.groups[0] = groups;
+    return J;
+}

@@ -922,7 +922,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == RG_EPI_GELU16 ? 4 : 1)) void rowgemm
     sei_wait_vmcnt<0>();                                  // the clamped stages still in flight
     if constexpr (LNB) {
         // column sums of this workgroup: [3][32 rows][48 quads] through the (now idle) ring, then 3 x 48 threads add up
-        // the 32 rows in a fixed order; [workgroup][3][nv] partials, folded by sei_fold_partials3
+        // the 32 rows in a fixed order; [workgroup][3][nv] partials, folded by sei_fold_now
         static_assert(3 * STAGE >= 3 * 32 * 48 * 16, "the ring holds the partial sums");
         __builtin_amdgcn_s_barrier();
         f32x4 *red = reinterpret_cast<f32x4 *>(smem);
@@ -1100,7 +1100,7 @@ extern "C" int sei_rowgemm_lnbwd_bf16(const uint16_t *A, int lda, const uint16_t
     else
         rc = y16 ? rg_launch<9, 12, 32, 4, 1, RG_EPI_LNBWD, true>(g, m, s) : rg_launch<9, 12, 32, 4, 1, RG_EPI_LNBWD, false>(g, m, s);
     if (rc != 0 || !ggamma) return rc;
-    return sei_fold_partials3(work, groups, C, ggamma, gbeta, colsum, s);
+    return sei_fold_now(sei_fold_job(SEI_FOLD_SPLIT, work, groups, 3 * C, C, ggamma, gbeta, colsum), s);
 }
 
 extern "C" size_t sei_rowgemm_dgelu_bf16_eligible(long long M, int N, int K) {

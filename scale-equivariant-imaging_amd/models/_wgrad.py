@@ -28,7 +28,8 @@ DWSTREAM = os.environ.get("SEI_NO_DWSTREAM") != "1"
 # the LayerNorm epilogue of SwinIR's data-gradient GEMMs) leave per-workgroup partial sums; instead of one ~5-us fold
 # launch behind each of them (52 per U-Net step, ~146 per SwinIR step) the partial sums are kept alive and ONE
 # sei_fold_many launch per <= 40 destinations adds them up when the backward pass ends (the engine callback that also
-# flushes parked weight gradients) -- same slices, same order, launches of one destination one after the other:
+# flushes parked weight gradients). Both ways run one device routine (fold_entries in csrc/reduce_kernels.hip, where the
+# order of the additions is stated; oracle/fold_order.py is its model), launches of one destination one after the other:
 # bit-identical gradients. Outside a backward pass (kernel-level tests calling the helpers directly) nothing is
 # deferred. SEI_NO_DEFERRED_FOLDS=1 restores the fold per launch.
 DEFERRED_FOLDS = os.environ.get("SEI_NO_DEFERRED_FOLDS") != "1"
