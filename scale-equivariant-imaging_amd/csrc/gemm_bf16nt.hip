@@ -38,60 +38,61 @@ constexpr int NWAVES = 8, NT = 512;
 __device__ __attribute__((aligned(16))) unsigned short g_zero_chunk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 struct NtArgs {
-    const unsigned short *A, *B;
-    float *D32;
-    unsigned short *D16;
-    int M, N, K, lda, ldb;     // lda / ldb: row strides in elements of A / B as stored
-    int epilogue;
-    const float *bias, *R1, *R2;
-    unsigned short *D2_16;     // BIAS_GELU: gelu(D) in bf16
-    int splitk, k_per_split;
-    int tiles_m, tiles_n;
-    int tiles_per_xcd, band;   // tile order: see the kernel prologue
+    // (every member has its default: an entry point names only what it uses, and what it leaves alone is null / zero)
+    const unsigned short *A = nullptr, *B = nullptr;
+    float *D32 = nullptr;
+    unsigned short *D16 = nullptr;
+    int M = 0, N = 0, K = 0, lda = 0, ldb = 0;     // lda / ldb: row strides in elements of A / B as stored
+    int epilogue = 0;
+    const float *bias = nullptr, *R1 = nullptr, *R2 = nullptr;
+    unsigned short *D2_16 = nullptr;     // BIAS_GELU: gelu(D) in bf16
+    int splitk = 1, k_per_split = 0;
+    int tiles_m = 0, tiles_n = 0;
+    int tiles_per_xcd = 0, band = 0;   // tile order: see the kernel prologue
     // second reduction segment of reduction-major operands: rows k >= k_seg come from A2 / B2 (row k - k_seg)
-    const unsigned short *A2, *B2;
-    int k_seg;
+    const unsigned short *A2 = nullptr, *B2 = nullptr;
+    int k_seg = 0;
     // host-side only (the kernels never read them): the caller's explicit tile / band choice of the _ex entry
     // points; 0 = the dispatcher decides. Per call, so the library holds no mutable state.
-    int force_tile, force_band;
+    int force_tile = 0, force_band = 0;
     // quadrant kernel, unsplit launches whose result is rounded to bf16 (sei_gemm_bf16nt_colsum): colsum[n] += sum_m of the
     // ROUNDED results D16[m][n] -- the bias gradient b2 = column sums of gh3 = (dY W3) gelu'(h3) without a pass over gh3.
-    float *colsum;
+    float *colsum = nullptr;
     // host-side only: sei_gemm_bf16nt_plan. Non-null: the dispatcher writes (family, BM, BN, K splits) there and launches
     // NOTHING -- the schedule a call with these shapes would take, for tests that pin the timed launch set.
-    unsigned long long *plan;
+    unsigned long long *plan = nullptr;
     // 3x3 convolution on a zero-bordered grid (sei_gemm_bf16nt_conv): K = 9 * conv_cin; k-tile kt reads A rows
     // shifted by conv_off[tap], tap = k / conv_cin, at column k - tap * conv_cin. conv_cin = 0: a plain GEMM.
-    int conv_cin;
-    int conv_off[9];
+    int conv_cin = 0;
+    int conv_off[9] = {};
     // Adam applied in the epilogue (sei_gemm_bf16nt_dw2_adam, ADAM instantiations only): the accumulator IS the
     // complete gradient of element (m, n); parameter, both moments and the bf16 shadow share D's (M, N) layout.
     // adam_h (device): beta1, beta2, eps, weight_decay, step_size, 1/sqrt(bias_correction2) of this step.
-    float *adam_p, *adam_m, *adam_v;
-    unsigned short *adam_p16;
-    const float *adam_h;
+    float *adam_p = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+    unsigned short *adam_p16 = nullptr;
+    const float *adam_h = nullptr;
     // A batch of GEMMs in one launch that differ in the ROW at which a reduction-major B starts and in their output
     // (sei_gemm_bf16nt_dw2_taps: the nine taps of a 3x3 convolution's weight gradient, every one the same dY against the
     // padded input grid shifted by the tap): batch t reads B / B2 from row batch_row[t] on and writes D32 + t * batch_ld.
-    int batch;
-    int batch_row[9];
-    long long batch_ld;
+    int batch = 1;
+    int batch_row[9] = {};
+    long long batch_ld = 0;
     // sei_gemm_bf16nt_conv_unpad (row-patch epilogue only): the M rows are the pixels of a zero-bordered (H + 2) x (W + 2)
     // grid per image; only interior rows are written, to row (b H + y - 1) W + x - 1 of D32 / R1 (the NHWC tensors),
     // with LeakyReLU(0.01) before the residual when unpad_act. unpad_W = 0: rows as they are.
-    int unpad_H, unpad_W, unpad_act;
+    int unpad_H = 0, unpad_W = 0, unpad_act = 0;
     // Split-K through slabs (quadrant kernel, sei_gemm_bf16nt_ws): every K slice of a tile stores its accumulators into its
     // slab of the caller's workspace (write-through), draws a ticket from the tile's counter, and the slice that draws the
     // last one adds the other slabs to its registers and runs the WHOLE epilogue (any epilogue: the sum is complete) --
     // no zero-fill launch, no float atomics (1.3 TB/s chip-wide: 29 us for a 288 x 128 tile's 147 KB per workgroup).
     // ws_cnt: one counter per tile, zero between launches (the last arriver puts it back); ws_slab: tiles x splits slabs
     // of BM x BN floats in accumulator order. nullptr: split launches add their tiles with float atomics as before.
-    float *ws_slab;
-    unsigned *ws_cnt;
+    float *ws_slab = nullptr;
+    unsigned *ws_cnt = nullptr;
     // host-side only: the caller's workspace as handed over, and an explicit number of K slices (0 = the dispatcher's)
-    void *ws;
-    size_t ws_bytes;
-    int force_splitk;
+    void *ws = nullptr;
+    size_t ws_bytes = 0;
+    int force_splitk = 0;
 };
 
 __device__ __forceinline__ float4 nt_load4(const float *p) {
@@ -925,73 +926,71 @@ bool pq_adam_auto(const NtArgs &) { return false; }
 
 extern "C" int sei_colsum_bf16(const uint16_t *X, float *out, size_t M, int N, void *stream);     // bf16_support.hip
 
-static int nt_entry(const uint16_t *A, int lda, int a_rmajor, const uint16_t *B, int ldb, int b_rmajor,
-                    float *D32, uint16_t *D16, int M, int N, int K, int epilogue, const float *bias,
-                    const float *R1, const float *R2, uint16_t *D2_16, int tile, int band,
-                    void *stream, unsigned long long *plan, float *colsum = nullptr, void *ws = nullptr,
-                    size_t ws_bytes = 0, int splitk = 0);
+// ---- builders: every entry point starts from NtArgs' defaults, fills its operands through one of these and then names the
+// few options that are its own. Each returns SEI_OK or SEI_ERR_BAD_ARG.
+namespace {
 
-// The column sums ride in the quadrant kernel's epilogue where the launch takes it unsplit with a bf16 result; any other
-// schedule is followed by the column-sum kernel over the result (same quantity, one more launch).
-static int nt_entry_colsum(const uint16_t *A, int lda, int a_rmajor, const uint16_t *B, int ldb, int b_rmajor,
-                           uint16_t *D16, int M, int N, int K, int epilogue, const float *R1, float *colsum, void *stream,
-                           void *ws = nullptr, size_t ws_bytes = 0, int tile = 0, int splitk = 0, int band = 0) {
-    unsigned long long plan = 0;
-    int rc = nt_entry(A, lda, a_rmajor, B, ldb, b_rmajor, nullptr, D16, M, N, K, epilogue, nullptr, R1, nullptr, nullptr, tile, band,
-                      stream, &plan, nullptr, ws, ws_bytes, splitk);
-    if (rc != SEI_OK) return rc;
-    // (unsplit, or split through slabs: the last arriver's epilogue sees the complete tile)
-    const bool rides = (plan >> 48) == 2 && ((plan & 0xFFFF) == 1 || (plan & 0x8000) != 0) && N % 4 == 0 &&
-                       (reinterpret_cast<uintptr_t>(colsum) & 15) == 0;
-    rc = nt_entry(A, lda, a_rmajor, B, ldb, b_rmajor, nullptr, D16, M, N, K, epilogue, nullptr, R1, nullptr, nullptr, tile, band,
-                  stream, nullptr, rides ? colsum : nullptr, ws, ws_bytes, splitk);
-    if (rc != SEI_OK || rides) return rc;
-    return sei_colsum_bf16(D16, colsum, (size_t)M, N, stream);
+// Operands of one reduction segment, as stored (what else sei_gemm_bf16nt requires of them: nt_check).
+int nt_fill_plain(NtArgs &g, const uint16_t *A, int lda, const uint16_t *B, int ldb, int M, int N, int K) {
+    SEI_REQUIRE(A && B && M > 0 && N > 0 && K > 0);
+    g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
+    g.A2 = A; g.B2 = B; g.k_seg = K;                       // one reduction segment
+    return SEI_OK;
 }
 
-static int nt_entry(const uint16_t *A, int lda, int a_rmajor, const uint16_t *B, int ldb, int b_rmajor,
-                    float *D32, uint16_t *D16, int M, int N, int K, int epilogue, const float *bias,
-                    const float *R1, const float *R2, uint16_t *D2_16, int tile, int band,
-                    void *stream, unsigned long long *plan, float *colsum, void *ws, size_t ws_bytes, int splitk) {
-    SEI_REQUIRE(A && B && (D32 || D16) && M > 0 && N > 0 && K > 0 && splitk >= 0);
-    SEI_REQUIRE(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0);
-    SEI_REQUIRE(lda >= (a_rmajor ? M : K) && ldb >= (b_rmajor ? N : K));
-    if (a_rmajor) SEI_REQUIRE(M % 8 == 0);
-    if (b_rmajor) SEI_REQUIRE(N % 8 == 0);
-    SEI_REQUIRE((((uintptr_t)A | (uintptr_t)B) & 15) == 0);
+// The dw2 family: both operands reduction-major, the reduction running over K1 rows of (A1, B1) and then K2 rows of
+// (A2, B2). k2_min: 1, or 0 where the second segment may be empty (sei_gemm_bf16nt_dw2_taps).
+int nt_fill_dw2(NtArgs &g, const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1, const uint16_t *B2, int ldb,
+                int M, int N, int K1, int K2, int k2_min) {
+    SEI_REQUIRE(A1 && A2 && B1 && B2 && M > 0 && N > 0 && K1 > 0 && K2 >= k2_min);
+    SEI_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= M && ldb >= N);
+    SEI_REQUIRE((K1 + K2) % 8 == 0);
+    SEI_REQUIRE((((uintptr_t)A1 | (uintptr_t)A2 | (uintptr_t)B1 | (uintptr_t)B2) & 15) == 0);
+    g.A = A1; g.B = B1; g.A2 = A2; g.B2 = B2; g.k_seg = K1;
+    g.M = M; g.N = N; g.K = K1 + K2; g.lda = lda; g.ldb = ldb;
+    return SEI_OK;
+}
+
+}  // namespace
+
+// What sei_gemm_bf16nt and its siblings require of a filled argument block, and the tile / band they fall back to where the
+// caller named none. Once per public call, before the dispatcher.
+static int nt_check(NtArgs &g, int a_rmajor, int b_rmajor) {
+    const int epilogue = g.epilogue;
+    SEI_REQUIRE(g.A && g.B && (g.D32 || g.D16) && g.M > 0 && g.N > 0 && g.K > 0 && g.force_splitk >= 0);
+    SEI_REQUIRE(g.K % 8 == 0 && g.lda % 8 == 0 && g.ldb % 8 == 0);
+    SEI_REQUIRE(g.lda >= (a_rmajor ? g.M : g.K) && g.ldb >= (b_rmajor ? g.N : g.K));
+    if (a_rmajor) SEI_REQUIRE(g.M % 8 == 0);
+    if (b_rmajor) SEI_REQUIRE(g.N % 8 == 0);
+    SEI_REQUIRE((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0);
     SEI_REQUIRE(epilogue == SEI_EPI_NONE || epilogue == SEI_EPI_BIAS || epilogue == SEI_EPI_BIAS_GELU ||
                 epilogue == SEI_EPI_BIAS_RES || epilogue == SEI_EPI_MUL_DGELU || epilogue == SEI_EPI_ACCUM ||
                 epilogue == SEI_EPI_BIAS_ROWSCALE || epilogue == SEI_EPI_BIAS_SCALE_RES);
     if (epilogue == SEI_EPI_BIAS || epilogue == SEI_EPI_BIAS_GELU || epilogue == SEI_EPI_BIAS_RES ||
         epilogue == SEI_EPI_BIAS_ROWSCALE || epilogue == SEI_EPI_BIAS_SCALE_RES)
-        SEI_REQUIRE(bias);
-    if (epilogue == SEI_EPI_BIAS_ROWSCALE) SEI_REQUIRE(R1);
-    if (epilogue == SEI_EPI_BIAS_SCALE_RES) SEI_REQUIRE(R1 && R2 && D32 && !a_rmajor && !b_rmajor);
-    if (epilogue == SEI_EPI_BIAS_GELU) SEI_REQUIRE(D2_16);
-    if (epilogue == SEI_EPI_BIAS_RES || epilogue == SEI_EPI_MUL_DGELU) SEI_REQUIRE(R1);
-    if (epilogue == SEI_EPI_ACCUM) SEI_REQUIRE(D32 && !D16);
-    NtArgs g; g.plan = nullptr; g.colsum = nullptr; g.unpad_H = 0; g.unpad_W = 0; g.unpad_act = 0;
-    g.ws_slab = nullptr; g.ws_cnt = nullptr; g.ws = nullptr; g.ws_bytes = 0; g.force_splitk = 0;
-    g.A = A; g.B = B; g.D32 = D32; g.D16 = D16; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-    g.epilogue = epilogue; g.bias = bias; g.R1 = R1; g.R2 = R2; g.D2_16 = D2_16;
-    g.A2 = A; g.B2 = B; g.k_seg = K;                       // one reduction segment
-    g.conv_cin = 0;
-    g.batch = 1;
-    g.plan = plan;
-    g.colsum = colsum;
-    g.ws = ws; g.ws_bytes = ws ? ws_bytes : 0; g.force_splitk = splitk;
-    SEI_REQUIRE(tile >= 0 && band >= 0);
-    if (epilogue == SEI_EPI_BIAS_SCALE_RES && tile == 0)                // the quadrant kernel has no such epilogue
-        tile = (N > 128 && N <= 192) ? 6 : 1;
+        SEI_REQUIRE(g.bias);
+    if (epilogue == SEI_EPI_BIAS_ROWSCALE) SEI_REQUIRE(g.R1);
+    if (epilogue == SEI_EPI_BIAS_SCALE_RES) SEI_REQUIRE(g.R1 && g.R2 && g.D32 && !a_rmajor && !b_rmajor);
+    if (epilogue == SEI_EPI_BIAS_GELU) SEI_REQUIRE(g.D2_16);
+    if (epilogue == SEI_EPI_BIAS_RES || epilogue == SEI_EPI_MUL_DGELU) SEI_REQUIRE(g.R1);
+    if (epilogue == SEI_EPI_ACCUM) SEI_REQUIRE(g.D32 && !g.D16);
+    SEI_REQUIRE(g.force_tile >= 0 && g.force_band >= 0);
+    if (!g.ws) g.ws_bytes = 0;
+    if (epilogue == SEI_EPI_BIAS_SCALE_RES && g.force_tile == 0)        // the quadrant kernel has no such epilogue
+        g.force_tile = (g.N > 128 && g.N <= 192) ? 6 : 1;
 #ifdef SEI_TUNING
-    if (tile == 0) tile = g_tuning_tile;
-    if (band == 0) band = g_tuning_band;
+    if (g.force_tile == 0) g.force_tile = g_tuning_tile;
+    if (g.force_band == 0) g.force_band = g_tuning_band;
 #endif
-    g.force_tile = tile;
-    g.force_band = band;
-    hipStream_t s = (hipStream_t)stream;
+    return SEI_OK;
+}
+
+// The dispatcher: launches the schedule for a checked argument block (or, with g.plan, only reports it). It settles the
+// schedule's fields in g, so every call gets a block of its own.
+static int nt_dispatch(NtArgs &g, int a_rmajor, int b_rmajor, hipStream_t s) {
+    const int tile = g.force_tile, epilogue = g.epilogue, M = g.M, N = g.N, K = g.K;
     const bool would_split = (epilogue == SEI_EPI_NONE || epilogue == SEI_EPI_BIAS || epilogue == SEI_EPI_BIAS_RES ||
-                              epilogue == SEI_EPI_ACCUM) && D32 && !D16;
+                              epilogue == SEI_EPI_ACCUM) && g.D32 && !g.D16;
     if (tile >= 30 && tile < 40 && a_rmajor && b_rmajor && pq_eligible(g, true)) {
         if (tile == 30) return launch_pq<8, 4, true, true>(g, s);
         if (tile == 33) return launch_pq<8, 2, true, true>(g, s);
@@ -1061,7 +1060,7 @@ static int nt_entry(const uint16_t *A, int lda, int a_rmajor, const uint16_t *B,
     }
     if (a_rmajor) return launch_nt<2, 1, 2, 4, true, false>(g, s);
     // (slabs serve every epilogue: also the convolution behind the downsampler, float32 out with its bias scaled per row)
-    const int slab_code = pq_choose_slabs(g, would_split || (epilogue == SEI_EPI_BIAS_ROWSCALE && D32 && !D16));
+    const int slab_code = pq_choose_slabs(g, would_split || (epilogue == SEI_EPI_BIAS_ROWSCALE && g.D32 && !g.D16));
     if (b_rmajor) {
         switch (slab_code ? slab_code : pq_choose(g, would_split)) {
             case 94: return launch_pq<9, 4, false, true>(g, s);
@@ -1114,19 +1113,45 @@ static int nt_entry(const uint16_t *A, int lda, int a_rmajor, const uint16_t *B,
     return launch_nt<2, 1, 2, 4>(g, s);                                                  // 128 x 128
 }
 
+static int nt_entry(NtArgs &g, int a_rmajor, int b_rmajor, hipStream_t s) {
+    const int rc = nt_check(g, a_rmajor, b_rmajor);
+    return rc != SEI_OK ? rc : nt_dispatch(g, a_rmajor, b_rmajor, s);
+}
+
+// The column sums ride in the quadrant kernel's epilogue where the launch takes it unsplit with a bf16 result; any other
+// schedule is followed by the column-sum kernel over the result (same quantity, one more launch).
+static int nt_entry_colsum(NtArgs &g, int a_rmajor, int b_rmajor, float *colsum, hipStream_t s) {
+    int rc = nt_check(g, a_rmajor, b_rmajor);
+    if (rc != SEI_OK) return rc;
+    unsigned long long plan = 0;
+    NtArgs query = g;
+    query.plan = &plan;
+    rc = nt_dispatch(query, a_rmajor, b_rmajor, s);
+    if (rc != SEI_OK) return rc;
+    // (unsplit, or split through slabs: the last arriver's epilogue sees the complete tile)
+    const bool rides = (plan >> 48) == 2 && ((plan & 0xFFFF) == 1 || (plan & 0x8000) != 0) && g.N % 4 == 0 &&
+                       (reinterpret_cast<uintptr_t>(colsum) & 15) == 0;
+    g.colsum = rides ? colsum : nullptr;
+    rc = nt_dispatch(g, a_rmajor, b_rmajor, s);
+    if (rc != SEI_OK || rides) return rc;
+    return sei_colsum_bf16(g.D16, colsum, (size_t)g.M, g.N, s);
+}
+
 extern "C" int sei_gemm_bf16nt_ex(const uint16_t *A, int lda, int a_rmajor, const uint16_t *B, int ldb, int b_rmajor,
                                   float *D32, uint16_t *D16, int M, int N, int K, int epilogue, const float *bias,
                                   const float *R1, const float *R2, uint16_t *D2_16, int tile, int band,
                                   void *stream) {
-    return nt_entry(A, lda, a_rmajor, B, ldb, b_rmajor, D32, D16, M, N, K, epilogue, bias, R1, R2, D2_16, tile, band,
-                    stream, nullptr);
+    NtArgs g;
+    SEI_REQUIRE(nt_fill_plain(g, A, lda, B, ldb, M, N, K) == SEI_OK);
+    g.D32 = D32; g.D16 = D16; g.epilogue = epilogue; g.bias = bias; g.R1 = R1; g.R2 = R2; g.D2_16 = D2_16;
+    g.force_tile = tile; g.force_band = band;
+    return nt_entry(g, a_rmajor, b_rmajor, (hipStream_t)stream);
 }
 
 extern "C" int sei_gemm_bf16nt(const uint16_t *A, int lda, int a_rmajor, const uint16_t *B, int ldb, int b_rmajor,
                                float *D32, uint16_t *D16, int M, int N, int K, int epilogue, const float *bias,
                                const float *R1, const float *R2, uint16_t *D2_16, void *stream) {
-    return nt_entry(A, lda, a_rmajor, B, ldb, b_rmajor, D32, D16, M, N, K, epilogue, bias, R1, R2, D2_16, 0, 0, stream,
-                    nullptr);
+    return sei_gemm_bf16nt_ex(A, lda, a_rmajor, B, ldb, b_rmajor, D32, D16, M, N, K, epilogue, bias, R1, R2, D2_16, 0, 0, stream);
 }
 
 // D16 = (A op(B)) gelu'(R1) rounded to bf16 (SEI_EPI_MUL_DGELU) or the plain product (SEI_EPI_NONE), and colsum[n] += the
@@ -1135,7 +1160,10 @@ extern "C" int sei_gemm_bf16nt_colsum(const uint16_t *A, int lda, int a_rmajor, 
                                       uint16_t *D16, int M, int N, int K, int epilogue, const float *R1, float *colsum,
                                       void *stream) {
     SEI_REQUIRE(D16 && colsum && (epilogue == SEI_EPI_MUL_DGELU || epilogue == SEI_EPI_NONE));
-    return nt_entry_colsum(A, lda, a_rmajor, B, ldb, b_rmajor, D16, M, N, K, epilogue, R1, colsum, stream);
+    NtArgs g;
+    SEI_REQUIRE(nt_fill_plain(g, A, lda, B, ldb, M, N, K) == SEI_OK);
+    g.D16 = D16; g.epilogue = epilogue; g.R1 = R1;
+    return nt_entry_colsum(g, a_rmajor, b_rmajor, colsum, (hipStream_t)stream);
 }
 
 // sei_gemm_bf16nt / sei_gemm_bf16nt_colsum with a split-K workspace (NtArgs::ws_slab): `ws` = ws_bytes of device memory,
@@ -1150,13 +1178,16 @@ extern "C" int sei_gemm_bf16nt_ws(const uint16_t *A, int lda, int a_rmajor, cons
                                   const float *R1, const float *R2, uint16_t *D2_16, float *colsum, void *ws,
                                   size_t ws_bytes, int tile, int band, int splitk, void *stream) {
     SEI_REQUIRE(tile >= 0 && band >= 0 && splitk >= 0 && (ws == nullptr || ws_bytes >= 16384));
+    NtArgs g;
+    SEI_REQUIRE(nt_fill_plain(g, A, lda, B, ldb, M, N, K) == SEI_OK);
+    g.D16 = D16; g.epilogue = epilogue; g.R1 = R1;
+    g.force_tile = tile; g.force_band = band; g.ws = ws; g.ws_bytes = ws_bytes; g.force_splitk = splitk;
     if (colsum) {
         SEI_REQUIRE(D16 && !D32 && (epilogue == SEI_EPI_MUL_DGELU || epilogue == SEI_EPI_NONE));
-        return nt_entry_colsum(A, lda, a_rmajor, B, ldb, b_rmajor, D16, M, N, K, epilogue, R1, colsum, stream, ws, ws_bytes,
-                               tile, splitk, band);
+        return nt_entry_colsum(g, a_rmajor, b_rmajor, colsum, (hipStream_t)stream);
     }
-    return nt_entry(A, lda, a_rmajor, B, ldb, b_rmajor, D32, D16, M, N, K, epilogue, bias, R1, R2, D2_16, tile, band, stream,
-                    nullptr, nullptr, ws, ws_bytes, splitk);
+    g.D32 = D32; g.bias = bias; g.R2 = R2; g.D2_16 = D2_16;
+    return nt_entry(g, a_rmajor, b_rmajor, (hipStream_t)stream);
 }
 
 // The schedule sei_gemm_bf16nt would take for these shapes, launching nothing (host arithmetic only, no GPU needed):
@@ -1164,7 +1195,28 @@ extern "C" int sei_gemm_bf16nt_ws(const uint16_t *A, int lda, int a_rmajor, cons
 // (gemm_bf16nt_kernel, whatever its tile), 2 = the quadrant schedule (gemm_bf16pq_kernel); 0 = arguments the entry point
 // would refuse. Operands are taken as densely packed and 16-byte aligned, which is what models/_ops.py passes.
 static size_t nt_plan(int a_rmajor, int b_rmajor, int out_f32, int out_bf16, int M, int N, int K, int epilogue,
-                      size_t ws_bytes);
+                      size_t ws_bytes) {
+    const uint16_t *fake16 = reinterpret_cast<const uint16_t *>(uintptr_t(1) << 20);      // never dereferenced
+    float *fake32 = reinterpret_cast<float *>(uintptr_t(1) << 20);
+    const bool with_bias = epilogue == SEI_EPI_BIAS || epilogue == SEI_EPI_BIAS_GELU || epilogue == SEI_EPI_BIAS_RES ||
+                           epilogue == SEI_EPI_BIAS_ROWSCALE || epilogue == SEI_EPI_BIAS_SCALE_RES;
+    const bool with_r1 = epilogue == SEI_EPI_BIAS_RES || epilogue == SEI_EPI_MUL_DGELU ||
+                         epilogue == SEI_EPI_BIAS_ROWSCALE || epilogue == SEI_EPI_BIAS_SCALE_RES;
+    unsigned long long plan = 0;
+    NtArgs g;
+    if (nt_fill_plain(g, fake16, a_rmajor ? M : K, fake16, b_rmajor ? N : K, M, N, K) != SEI_OK) return 0;
+    g.D32 = out_f32 ? fake32 : nullptr;
+    g.D16 = out_bf16 ? const_cast<uint16_t *>(fake16) : nullptr;
+    g.epilogue = epilogue;
+    g.bias = with_bias ? fake32 : nullptr;
+    g.R1 = with_r1 ? fake32 : nullptr;
+    g.R2 = epilogue == SEI_EPI_BIAS_SCALE_RES ? fake32 : nullptr;
+    g.D2_16 = epilogue == SEI_EPI_BIAS_GELU ? const_cast<uint16_t *>(fake16) : nullptr;
+    g.ws = ws_bytes ? fake32 : nullptr;
+    g.ws_bytes = ws_bytes;
+    g.plan = &plan;
+    return nt_entry(g, a_rmajor, b_rmajor, nullptr) == SEI_OK ? (size_t)plan : 0;
+}
 extern "C" size_t sei_gemm_bf16nt_plan(int a_rmajor, int b_rmajor, int out_f32, int out_bf16, int M, int N, int K,
                                        int epilogue) {
     return nt_plan(a_rmajor, b_rmajor, out_f32, out_bf16, M, N, K, epilogue, 0);
@@ -1175,42 +1227,14 @@ extern "C" size_t sei_gemm_bf16nt_plan_ws(int a_rmajor, int b_rmajor, int out_f3
                                           int epilogue, size_t ws_bytes) {
     return nt_plan(a_rmajor, b_rmajor, out_f32, out_bf16, M, N, K, epilogue, ws_bytes);
 }
-static size_t nt_plan(int a_rmajor, int b_rmajor, int out_f32, int out_bf16, int M, int N, int K, int epilogue,
-                      size_t ws_bytes) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const uint16_t *fake16 = reinterpret_cast<const uint16_t *>(uintptr_t(1) << 20);      // never dereferenced
-    float *fake32 = reinterpret_cast<float *>(uintptr_t(1) << 20);
-    const bool with_bias = epilogue == SEI_EPI_BIAS || epilogue == SEI_EPI_BIAS_GELU || epilogue == SEI_EPI_BIAS_RES ||
-                           epilogue == SEI_EPI_BIAS_ROWSCALE || epilogue == SEI_EPI_BIAS_SCALE_RES;
-    const bool with_r1 = epilogue == SEI_EPI_BIAS_RES || epilogue == SEI_EPI_MUL_DGELU ||
-                         epilogue == SEI_EPI_BIAS_ROWSCALE || epilogue == SEI_EPI_BIAS_SCALE_RES;
-    unsigned long long plan = 0;
-    const int rc = nt_entry(fake16, a_rmajor ? M : K, a_rmajor, fake16, b_rmajor ? N : K, b_rmajor,
-                            out_f32 ? fake32 : nullptr, out_bf16 ? const_cast<uint16_t *>(fake16) : nullptr, M, N, K,
-                            epilogue, with_bias ? fake32 : nullptr, with_r1 ? fake32 : nullptr,
-                            epilogue == SEI_EPI_BIAS_SCALE_RES ? fake32 : nullptr,
-                            epilogue == SEI_EPI_BIAS_GELU ? const_cast<uint16_t *>(fake16) : nullptr, 0, 0, nullptr, &plan,
-                            nullptr, ws_bytes ? fake32 : nullptr, ws_bytes, 0);
-    return rc == SEI_OK ? (size_t)plan : 0;
-}
 
 extern "C" int sei_gemm_bf16nt_dw2_ex(const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1,
                                       const uint16_t *B2, int ldb, float *D32, int M, int N, int K1, int K2,
                                       int accumulate, int tile, void *stream) {
-    SEI_REQUIRE(A1 && A2 && B1 && B2 && D32 && M > 0 && N > 0 && K1 > 0 && K2 > 0);
-    SEI_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= M && ldb >= N);
-    SEI_REQUIRE((K1 + K2) % 8 == 0);
-    SEI_REQUIRE((((uintptr_t)A1 | (uintptr_t)A2 | (uintptr_t)B1 | (uintptr_t)B2) & 15) == 0);
-    NtArgs g; g.plan = nullptr; g.colsum = nullptr; g.unpad_H = 0; g.unpad_W = 0; g.unpad_act = 0;
-    g.ws_slab = nullptr; g.ws_cnt = nullptr; g.ws = nullptr; g.ws_bytes = 0; g.force_splitk = 0;
-    g.A = A1; g.B = B1; g.A2 = A2; g.B2 = B2; g.k_seg = K1;
-    g.D32 = D32; g.D16 = nullptr; g.M = M; g.N = N; g.K = K1 + K2; g.lda = lda; g.ldb = ldb;
+    NtArgs g;
+    SEI_REQUIRE(D32 && tile >= 0 && nt_fill_dw2(g, A1, A2, lda, B1, B2, ldb, M, N, K1, K2, 1) == SEI_OK);
+    g.D32 = D32;
     g.epilogue = accumulate ? SEI_EPI_ACCUM : SEI_EPI_NONE;
-    g.bias = nullptr; g.R1 = nullptr; g.R2 = nullptr; g.D2_16 = nullptr;
-    g.conv_cin = 0;
-    g.batch = 1;
-    SEI_REQUIRE(tile >= 0);
-    g.force_band = 0;
 #ifdef SEI_TUNING
     if (tile == 0) tile = g_tuning_tile;
     g.force_band = g_tuning_band;
@@ -1235,21 +1259,11 @@ extern "C" int sei_gemm_bf16nt_dw2_adam_ex(const uint16_t *A1, const uint16_t *A
                                            const uint16_t *B2, int ldb, float *param, float *exp_avg, float *exp_avg_sq,
                                            uint16_t *param_bf16, const float *hyper, int M, int N, int K1, int K2,
                                            int tile, void *stream) {
-    SEI_REQUIRE(A1 && A2 && B1 && B2 && param && exp_avg && exp_avg_sq && hyper && M > 0 && N > 0 && K1 > 0 && K2 > 0);
-    SEI_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= M && ldb >= N);
-    SEI_REQUIRE((K1 + K2) % 8 == 0);
-    SEI_REQUIRE((((uintptr_t)A1 | (uintptr_t)A2 | (uintptr_t)B1 | (uintptr_t)B2) & 15) == 0);
+    NtArgs g;
+    SEI_REQUIRE(param && exp_avg && exp_avg_sq && hyper && nt_fill_dw2(g, A1, A2, lda, B1, B2, ldb, M, N, K1, K2, 1) == SEI_OK);
     SEI_REQUIRE((((uintptr_t)param | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0 &&
                 ((uintptr_t)param_bf16 & 7) == 0);              // the epilogue moves whole quads
-    NtArgs g; g.plan = nullptr; g.colsum = nullptr; g.unpad_H = 0; g.unpad_W = 0; g.unpad_act = 0;
-    g.ws_slab = nullptr; g.ws_cnt = nullptr; g.ws = nullptr; g.ws_bytes = 0; g.force_splitk = 0;
-    g.A = A1; g.B = B1; g.A2 = A2; g.B2 = B2; g.k_seg = K1;
-    g.D32 = param; g.D16 = nullptr; g.M = M; g.N = N; g.K = K1 + K2; g.lda = lda; g.ldb = ldb;
-    g.epilogue = SEI_EPI_NONE;
-    g.bias = nullptr; g.R1 = nullptr; g.R2 = nullptr; g.D2_16 = nullptr;
-    g.conv_cin = 0;
-    g.batch = 1;
-    g.force_tile = 0; g.force_band = 0;
+    g.D32 = param;
     g.adam_p = param; g.adam_m = exp_avg; g.adam_v = exp_avg_sq; g.adam_p16 = param_bf16; g.adam_h = hyper;
     SEI_REQUIRE(tile == 0 || tile == 1 || tile == 30 || tile == 33);
     // tile 30 / 33: the quadrant schedule's 256 x 256 / 256 x 128 tiles with the Adam epilogue (round 5): half the operand
@@ -1274,20 +1288,9 @@ extern "C" int sei_gemm_bf16nt_dw2_adam(const uint16_t *A1, const uint16_t *A2, 
 extern "C" int sei_gemm_bf16nt_dw2_bf16out(const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1,
                                            const uint16_t *B2, int ldb, uint16_t *D16, int M, int N, int K1, int K2,
                                            void *stream) {
-    SEI_REQUIRE(A1 && A2 && B1 && B2 && D16 && M > 0 && N > 0 && K1 > 0 && K2 > 0);
-    SEI_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= M && ldb >= N);
-    SEI_REQUIRE((K1 + K2) % 8 == 0);
-    SEI_REQUIRE((((uintptr_t)A1 | (uintptr_t)A2 | (uintptr_t)B1 | (uintptr_t)B2) & 15) == 0 && ((uintptr_t)D16 & 7) == 0);
-    NtArgs g; g.plan = nullptr; g.colsum = nullptr; g.unpad_H = 0; g.unpad_W = 0; g.unpad_act = 0;
-    g.ws_slab = nullptr; g.ws_cnt = nullptr; g.ws = nullptr; g.ws_bytes = 0; g.force_splitk = 0;
-    g.A = A1; g.B = B1; g.A2 = A2; g.B2 = B2; g.k_seg = K1;
-    g.D32 = nullptr; g.D16 = D16; g.M = M; g.N = N; g.K = K1 + K2; g.lda = lda; g.ldb = ldb;
-    g.epilogue = SEI_EPI_NONE;
-    g.bias = nullptr; g.R1 = nullptr; g.R2 = nullptr; g.D2_16 = nullptr;
-    g.conv_cin = 0;
-    g.batch = 1;
-    g.force_tile = 0; g.force_band = 0;
-    g.adam_p = nullptr; g.adam_m = nullptr; g.adam_v = nullptr; g.adam_p16 = nullptr; g.adam_h = nullptr;
+    NtArgs g;
+    SEI_REQUIRE(D16 && ((uintptr_t)D16 & 7) == 0 && nt_fill_dw2(g, A1, A2, lda, B1, B2, ldb, M, N, K1, K2, 1) == SEI_OK);
+    g.D16 = D16;
     if (K1 + K2 <= 1024) return launch_nt<2, 1, 2, 4, true, true, 1, 2>(g, (hipStream_t)stream);
     return launch_nt<2, 1, 2, 4, true, true, 2, 2>(g, (hipStream_t)stream);
 }
@@ -1295,21 +1298,13 @@ extern "C" int sei_gemm_bf16nt_dw2_bf16out(const uint16_t *A1, const uint16_t *A
 extern "C" int sei_gemm_bf16nt_dw2_taps(const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1,
                                         const uint16_t *B2, int ldb, float *D32, int M, int N, int K1, int K2,
                                         int accumulate, int ntaps, const int *tap_rows, long long tap_ld, void *stream) {
-    SEI_REQUIRE(A1 && A2 && B1 && B2 && D32 && tap_rows && M > 0 && N > 0 && K1 > 0 && K2 >= 0);
+    NtArgs g;
+    SEI_REQUIRE(D32 && tap_rows && nt_fill_dw2(g, A1, A2, lda, B1, B2, ldb, M, N, K1, K2, 0) == SEI_OK);
     SEI_REQUIRE(ntaps >= 1 && ntaps <= 9 && tap_ld >= (long long)M * N);
-    SEI_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= M && ldb >= N);
-    SEI_REQUIRE((K1 + K2) % 8 == 0);
-    SEI_REQUIRE((((uintptr_t)A1 | (uintptr_t)A2 | (uintptr_t)B1 | (uintptr_t)B2) & 15) == 0);
-    NtArgs g; g.plan = nullptr; g.colsum = nullptr; g.unpad_H = 0; g.unpad_W = 0; g.unpad_act = 0;
-    g.ws_slab = nullptr; g.ws_cnt = nullptr; g.ws = nullptr; g.ws_bytes = 0; g.force_splitk = 0;
-    g.A = A1; g.B = B1; g.A2 = A2; g.B2 = B2; g.k_seg = K1;
-    g.D32 = D32; g.D16 = nullptr; g.M = M; g.N = N; g.K = K1 + K2; g.lda = lda; g.ldb = ldb;
+    g.D32 = D32;
     g.epilogue = accumulate ? SEI_EPI_ACCUM : SEI_EPI_NONE;
-    g.bias = nullptr; g.R1 = nullptr; g.R2 = nullptr; g.D2_16 = nullptr;
-    g.conv_cin = 0;
-    g.force_tile = 0; g.force_band = 0;
     g.batch = ntaps;
-    for (int t = 0; t < 9; ++t) g.batch_row[t] = t < ntaps ? tap_rows[t] : 0;
+    for (int t = 0; t < ntaps; ++t) g.batch_row[t] = tap_rows[t];
     g.batch_ld = tap_ld;
     return launch_nt<2, 1, 2, 4, true, true, 2, 3>(g, (hipStream_t)stream);
 }
@@ -1320,6 +1315,24 @@ extern "C" int sei_gemm_bf16nt_dw2(const uint16_t *A1, const uint16_t *A2, int l
     return sei_gemm_bf16nt_dw2_ex(A1, A2, lda, B1, B2, ldb, D32, M, N, K1, K2, accumulate, 0, stream);
 }
 
+namespace {
+
+// 3x3 convolution on the zero-bordered grid (NtArgs::conv_cin): the M rows of Ap are the grid's pixels, cin_pad channels
+// each; B holds the nine taps' weights side by side.
+int nt_fill_conv(NtArgs &g, const uint16_t *Ap, int cin_pad, const int *row_off9, const uint16_t *B, int ldb, int M, int N) {
+    SEI_REQUIRE(row_off9 && cin_pad > 0 && cin_pad % BK == 0 && nt_fill_plain(g, Ap, cin_pad, B, ldb, M, N, 9 * cin_pad) == SEI_OK);
+    SEI_REQUIRE(ldb >= 9 * cin_pad && ldb % 8 == 0 && (((uintptr_t)Ap | (uintptr_t)B) & 15) == 0);
+    g.conv_cin = cin_pad;
+    for (int t = 0; t < 9; ++t) g.conv_off[t] = row_off9[t];
+    return SEI_OK;
+}
+int nt_launch_conv(NtArgs &g, hipStream_t s) {
+    if (g.N > 128 && g.N <= 192) return launch_nt<1, 3, 4, 2>(g, s);           // 128 x 192: one column tile
+    return launch_nt<2, 1, 2, 4>(g, s);
+}
+
+}  // namespace
+
 // 3x3 convolution (stride 1, zero padding 1) of an NHWC batch as ONE implicit GEMM on the zero-bordered grid of
 // sei_pad_nhwc_bf16: output row r (a pixel of the padded grid) = sum over taps t and channels c of
 // Ap[r + row_off[t]][c] * B[n][t * cin_pad + c]. The im2col matrix exists only as LDS tiles: each k-tile of the
@@ -1327,22 +1340,11 @@ extern "C" int sei_gemm_bf16nt_dw2(const uint16_t *A1, const uint16_t *A2, int l
 extern "C" int sei_gemm_bf16nt_conv(const uint16_t *Ap, int cin_pad, const int *row_off9, const uint16_t *B, int ldb,
                                     float *D32, uint16_t *D16, int M, int N, int epilogue, const float *bias,
                                     void *stream) {
-    SEI_REQUIRE(Ap && row_off9 && B && (D32 || D16) && M > 0 && N > 0 && cin_pad > 0 && cin_pad % BK == 0);
-    SEI_REQUIRE(ldb >= 9 * cin_pad && ldb % 8 == 0 && (((uintptr_t)Ap | (uintptr_t)B) & 15) == 0);
-    SEI_REQUIRE(epilogue == SEI_EPI_NONE || epilogue == SEI_EPI_BIAS);
-    if (epilogue == SEI_EPI_BIAS) SEI_REQUIRE(bias);
-    NtArgs g; g.plan = nullptr; g.colsum = nullptr; g.unpad_H = 0; g.unpad_W = 0; g.unpad_act = 0;
-    g.ws_slab = nullptr; g.ws_cnt = nullptr; g.ws = nullptr; g.ws_bytes = 0; g.force_splitk = 0;
-    g.batch = 1;
-    g.A = Ap; g.B = B; g.D32 = D32; g.D16 = D16; g.M = M; g.N = N; g.K = 9 * cin_pad; g.lda = cin_pad; g.ldb = ldb;
-    g.epilogue = epilogue; g.bias = bias; g.R1 = nullptr; g.R2 = nullptr; g.D2_16 = nullptr;
-    g.A2 = Ap; g.B2 = B; g.k_seg = g.K;
-    g.force_tile = 0; g.force_band = 0;
-    g.conv_cin = cin_pad;
-    for (int t = 0; t < 9; ++t) g.conv_off[t] = row_off9[t];
-    hipStream_t s = (hipStream_t)stream;
-    if (N > 128 && N <= 192) return launch_nt<1, 3, 4, 2>(g, s);               // 128 x 192: one column tile
-    return launch_nt<2, 1, 2, 4>(g, s);
+    SEI_REQUIRE((D32 || D16) && (epilogue == SEI_EPI_NONE || (epilogue == SEI_EPI_BIAS && bias)));
+    NtArgs g;
+    SEI_REQUIRE(nt_fill_conv(g, Ap, cin_pad, row_off9, B, ldb, M, N) == SEI_OK);
+    g.D32 = D32; g.D16 = D16; g.epilogue = epilogue; g.bias = bias;
+    return nt_launch_conv(g, (hipStream_t)stream);
 }
 
 // The same convolution with sei_unpad_nhwc in its epilogue: y (Bimg, H, W, N) = [LeakyReLU](conv + bias) [+ res], the
@@ -1350,26 +1352,15 @@ extern "C" int sei_gemm_bf16nt_conv(const uint16_t *Ap, int cin_pad, const int *
 extern "C" int sei_gemm_bf16nt_conv_unpad(const uint16_t *Ap, int cin_pad, const int *row_off9, const uint16_t *B, int ldb,
                                           float *y, const float *res, int Bimg, int H, int W, int N, const float *bias,
                                           int act, void *stream) {
-    SEI_REQUIRE(Ap && row_off9 && B && y && Bimg > 0 && H > 0 && W > 0 && N > 0 && N % 4 == 0 && cin_pad > 0 && cin_pad % BK == 0);
-    SEI_REQUIRE(ldb >= 9 * cin_pad && ldb % 8 == 0 && (((uintptr_t)Ap | (uintptr_t)B) & 15) == 0);
+    SEI_REQUIRE(y && Bimg > 0 && H > 0 && W > 0 && N % 4 == 0);
     SEI_REQUIRE((((uintptr_t)y | (uintptr_t)res) & 15) == 0 && (act == 0 || act == 1));
     SEI_REQUIRE((size_t)Bimg * (H + 2) * (W + 2) < ((size_t)1 << 31));
-    NtArgs g;
-    g.plan = nullptr;
-    g.colsum = nullptr;
-    g.ws_slab = nullptr; g.ws_cnt = nullptr; g.ws = nullptr; g.ws_bytes = 0; g.force_splitk = 0;
-    g.batch = 1;
-    g.A = Ap; g.B = B; g.D32 = y; g.D16 = nullptr; g.M = Bimg * (H + 2) * (W + 2); g.N = N; g.K = 9 * cin_pad;
-    g.lda = cin_pad; g.ldb = ldb;
-    g.epilogue = res ? SEI_EPI_BIAS_RES : (bias ? SEI_EPI_BIAS : SEI_EPI_NONE);
-    g.bias = bias; g.R1 = res; g.R2 = nullptr; g.D2_16 = nullptr;
     if (res && !bias) return SEI_ERR_BAD_ARG;               // (every residual convolution of the backbones has a bias)
-    g.A2 = Ap; g.B2 = B; g.k_seg = g.K;
-    g.force_tile = 0; g.force_band = 0;
-    g.conv_cin = cin_pad;
-    for (int t = 0; t < 9; ++t) g.conv_off[t] = row_off9[t];
+    NtArgs g;
+    SEI_REQUIRE(nt_fill_conv(g, Ap, cin_pad, row_off9, B, ldb, Bimg * (H + 2) * (W + 2), N) == SEI_OK);
+    g.D32 = y;
+    g.epilogue = res ? SEI_EPI_BIAS_RES : (bias ? SEI_EPI_BIAS : SEI_EPI_NONE);
+    g.bias = bias; g.R1 = res;
     g.unpad_H = H; g.unpad_W = W; g.unpad_act = act;
-    hipStream_t s = (hipStream_t)stream;
-    if (N > 128 && N <= 192) return launch_nt<1, 3, 4, 2>(g, s);
-    return launch_nt<2, 1, 2, 4>(g, s);
+    return nt_launch_conv(g, (hipStream_t)stream);
 }

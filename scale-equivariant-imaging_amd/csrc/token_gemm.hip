@@ -328,32 +328,33 @@ __global__ __launch_bounds__(512, 2) void tokgrad_regs_kernel(TokGradArgs g) {
 constexpr int RG_NT = 512;
 
 struct RowGemmArgs {
-    const unsigned short *A, *W;
-    int lda, ldw;
-    int tiles;                // M / TR
-    const float *bias;        // nv entries or nullptr
-    const float *R1, *R2;     // BIAS_RES: R1 (+ R2) residual rows; BIAS_SCALE_RES: R1 = one factor per row, R2 = residual rows;
-    int ldr;                  // MUL_DGELU: R1 = the GELU' input rows.  Row stride of the row-shaped one(s)
-    float *D32;
-    unsigned short *D16;      // the result in bf16 (BIAS, NONE, MUL_DGELU) / gelu(result) in bf16 (BIAS_GELU)
-    int ld32, ld16;
-    int nv;                   // valid output columns of D32 / R (a multiple of 4); D16 always gets all 64 NB columns
+    // (every member has its default: an entry point names only what it uses)
+    const unsigned short *A = nullptr, *W = nullptr;
+    int lda = 0, ldw = 0;
+    int tiles = 0;            // M / TR
+    const float *bias = nullptr;                  // nv entries or nullptr
+    const float *R1 = nullptr, *R2 = nullptr;     // BIAS_RES: R1 (+ R2) residual rows; BIAS_SCALE_RES: R1 = one factor per row, R2 = residual rows;
+    int ldr = 0;              // MUL_DGELU: R1 = the GELU' input rows.  Row stride of the row-shaped one(s)
+    float *D32 = nullptr;
+    unsigned short *D16 = nullptr;                // the result in bf16 (BIAS, NONE, MUL_DGELU) / gelu(result) in bf16 (BIAS_GELU)
+    int ld32 = 0, ld16 = 0;
+    int nv = 0;               // valid output columns of D32 / R (a multiple of 4); D16 always gets all 64 NB columns
     // RG_EPI_LNBWD (the product is the gradient with respect to a LayerNorm's output): the norm's input rows (R1, ldr),
     // its statistics and weight, the residual gradient rows (R2, ldr); D32 = the gradient with respect to the input;
     // optionally D16 = bf16(D32 * scale[row]) in 192-column rows; part: [workgroup][3][nv] column sums
-    const float *mean, *rstd, *gamma, *scale;
-    float *part;
+    const float *mean = nullptr, *rstd = nullptr, *gamma = nullptr, *scale = nullptr;
+    float *part = nullptr;
     // RG_EPI_DGELU2 (D16 = bf16((A W^T) gelu'(A2 W2^T + bias))): the second product's operands -- the GELU' input is
     // RECOMPUTED from the layer's input rows instead of being stored by the forward pass and read back
-    const unsigned short *A2, *W2;
-    int lda2, ldw2;
+    const unsigned short *A2 = nullptr, *W2 = nullptr;
+    int lda2 = 0, ldw2 = 0;
     // RG_EPI_*_LN: the LayerNorm that follows the residual sum (weight gamma, bias beta2, eps): D16 = its output in bf16
     // rows (ones_col: 1.0 in padding column nv), mean / rstd written through mean_out / rstd_out
-    const float *beta2;
-    float *mean_out, *rstd_out;
-    float eps;
-    int ones_col;
-    int gelu_one_at;          // SEI_EPI_BIAS_GELU: this column of D16 is written as 1.0 (-1: none)
+    const float *beta2 = nullptr;
+    float *mean_out = nullptr, *rstd_out = nullptr;
+    float eps = 0.f;
+    int ones_col = 0;
+    int gelu_one_at = -1;     // SEI_EPI_BIAS_GELU: this column of D16 is written as 1.0 (-1: none)
 };
 
 constexpr int RG_EPI_LNBWD = 100;     // internal epilogue codes (sei_rowgemm_lnbwd_bf16, sei_rowgemm_dgelu_bf16,
@@ -951,6 +952,19 @@ int rg_launch(const RowGemmArgs &g, int M, hipStream_t s, int per_cu = 1) {
     return sei_launch_status();
 }
 
+// What the row-GEMM kernel requires of a product's operands: K-contiguous rows on the 8-element grid, 16-byte aligned, the 64
+// rows of a tile of A within 32-bit byte offsets ...
+bool rg_operands_ok(const uint16_t *A, int lda, const uint16_t *W, int ldw, int K) {
+    return A && W && lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 && (((uintptr_t)A | (uintptr_t)W) & 15) == 0 &&
+           (unsigned long long)64 * (size_t)lda * 2 < (1ull << 32);
+}
+// ... and the operands every sei_rowgemm_* entry point takes, over whole 64-row tiles.
+int rg_fill_operands(RowGemmArgs &g, const uint16_t *A, int lda, const uint16_t *W, int ldw, long long M, int K) {
+    SEI_REQUIRE(M > 0 && M % 64 == 0 && M < (1ll << 31) && rg_operands_ok(A, lda, W, ldw, K));
+    g.A = A; g.W = W; g.lda = lda; g.ldw = ldw;
+    return SEI_OK;
+}
+
 bool tg_block_ok(const SeiTokGradBlock &b, long long K2) {
     if (!b.Y1 || !b.X1 || !b.D || (K2 && (!b.Y2 || !b.X2))) return false;
     if (b.ldy % 8 || b.ldx % 8 || b.y0 % 8 || b.x0 % 8 || b.y0 < 0 || b.x0 < 0) return false;
@@ -1030,11 +1044,9 @@ extern "C" int sei_rowgemm_bf16(const uint16_t *A, int lda, const uint16_t *W, i
                                 uint16_t *D16, int ld16, long long M, int N, int K, int nv, int epilogue,
                                 const float *bias, const float *R1, const float *R2, int ldr, void *stream) {
     const int out16 = (D16 != nullptr && D32 == nullptr) ? 1 : 0;
-    SEI_REQUIRE(A && W && sei_rowgemm_bf16_eligible(M, N, K, epilogue, out16));
-    SEI_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0);
-    SEI_REQUIRE((((uintptr_t)A | (uintptr_t)W) & 15) == 0);
+    RowGemmArgs g;
+    SEI_REQUIRE(sei_rowgemm_bf16_eligible(M, N, K, epilogue, out16) && rg_fill_operands(g, A, lda, W, ldw, M, K) == SEI_OK);
     SEI_REQUIRE(nv > 0 && nv <= N && nv % 4 == 0);
-    SEI_REQUIRE((unsigned long long)64 * (size_t)lda * 2 < (1ull << 32));
     const bool has_bias = epilogue == SEI_EPI_BIAS || epilogue == SEI_EPI_BIAS_GELU || epilogue == SEI_EPI_BIAS_RES ||
                           epilogue == SEI_EPI_BIAS_SCALE_RES;
     SEI_REQUIRE(!has_bias || bias);
@@ -1044,9 +1056,8 @@ extern "C" int sei_rowgemm_bf16(const uint16_t *A, int lda, const uint16_t *W, i
     if (epilogue == SEI_EPI_BIAS_RES || epilogue == SEI_EPI_MUL_DGELU)
         SEI_REQUIRE(R1 && !R2 && ldr >= nv && ldr % 4 == 0 && ((uintptr_t)R1 & 15) == 0);
     if (epilogue == SEI_EPI_BIAS_SCALE_RES) SEI_REQUIRE(R1 && R2 && ldr >= nv && ldr % 4 == 0 && ((uintptr_t)R2 & 15) == 0);
-    RowGemmArgs g;
-    g.A = A; g.W = W; g.lda = lda; g.ldw = ldw; g.tiles = 0; g.bias = bias; g.R1 = R1; g.R2 = R2; g.ldr = ldr;
-    g.D32 = D32; g.D16 = D16; g.ld32 = ld32; g.ld16 = ld16; g.nv = nv; g.gelu_one_at = -1;
+    g.bias = bias; g.R1 = R1; g.R2 = R2; g.ldr = ldr;
+    g.D32 = D32; g.D16 = D16; g.ld32 = ld32; g.ld16 = ld16; g.nv = nv;
     hipStream_t s = (hipStream_t)stream;
     const int m = (int)M;
     // <k-tiles, 16-column blocks, rows per tile, column groups, row groups>
@@ -1080,16 +1091,15 @@ extern "C" int sei_rowgemm_lnbwd_bf16(const uint16_t *A, int lda, const uint16_t
                                       int C, float *ggamma, float *gbeta, const float *row_scale, uint16_t *y16, int ldy,
                                       float *colsum, float *work, size_t work_floats, void *stream) {
     // ggamma = gbeta = NULL: the partial sums ([min(M / 32, 256)][3][C]) stay in `work` for sei_fold_many
-    SEI_REQUIRE(A && W && x && gamma && mean && rstd && res && gx && work && (ggamma != nullptr) == (gbeta != nullptr));
+    RowGemmArgs g;
+    SEI_REQUIRE(x && gamma && mean && rstd && res && gx && work && (ggamma != nullptr) == (gbeta != nullptr));
     SEI_REQUIRE(sei_rowgemm_lnbwd_bf16_eligible(M, K, C) && work_floats >= sei_rowgemm_lnbwd_work_floats(C));
-    SEI_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 && (((uintptr_t)A | (uintptr_t)W) & 15) == 0);
-    SEI_REQUIRE((unsigned long long)64 * (size_t)lda * 2 < (1ull << 32));
+    SEI_REQUIRE(rg_fill_operands(g, A, lda, W, ldw, M, K) == SEI_OK);
     SEI_REQUIRE((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)res | (uintptr_t)gx | (uintptr_t)work) & 15) == 0);
     SEI_REQUIRE((y16 != nullptr) == (row_scale != nullptr) && (!colsum || y16));
     SEI_REQUIRE(!colsum || K == 384);         // (K = 576: the bf16 copy without its column sums -- no registers left for them)
     if (y16) SEI_REQUIRE(ldy >= 192 && ldy % 4 == 0 && ((uintptr_t)y16 & 7) == 0);
-    RowGemmArgs g;
-    g.A = A; g.W = W; g.lda = lda; g.ldw = ldw; g.tiles = 0; g.bias = nullptr; g.R1 = x; g.R2 = res; g.ldr = C;
+    g.R1 = x; g.R2 = res; g.ldr = C;
     g.D32 = gx; g.D16 = y16; g.ld32 = C; g.ld16 = ldy; g.nv = C;
     g.mean = mean; g.rstd = rstd; g.gamma = gamma; g.scale = row_scale; g.part = work;
     hipStream_t s = (hipStream_t)stream;
@@ -1110,13 +1120,11 @@ extern "C" size_t sei_rowgemm_dgelu_bf16_eligible(long long M, int N, int K) {
 extern "C" int sei_rowgemm_dgelu_bf16(const uint16_t *A, int lda, const uint16_t *W, int ldw, const uint16_t *A2, int lda2,
                                       const uint16_t *W2, int ldw2, const float *bias2, int nv, uint16_t *D16, int ld16,
                                       long long M, int N, int K, void *stream) {
-    SEI_REQUIRE(A && W && A2 && W2 && bias2 && D16 && sei_rowgemm_dgelu_bf16_eligible(M, N, K));
-    SEI_REQUIRE(lda >= K && ldw >= K && lda2 >= K && ldw2 >= K && lda % 8 == 0 && ldw % 8 == 0 && lda2 % 8 == 0 && ldw2 % 8 == 0);
-    SEI_REQUIRE((((uintptr_t)A | (uintptr_t)W | (uintptr_t)A2 | (uintptr_t)W2 | (uintptr_t)D16) & 15) == 0);
-    SEI_REQUIRE(nv > 0 && nv <= N && ld16 >= N && ld16 % 8 == 0);
-    SEI_REQUIRE((unsigned long long)64 * (size_t)lda * 2 < (1ull << 32) && (unsigned long long)64 * (size_t)lda2 * 2 < (1ull << 32));
-    RowGemmArgs g = {};
-    g.A = A; g.W = W; g.lda = lda; g.ldw = ldw; g.A2 = A2; g.W2 = W2; g.lda2 = lda2; g.ldw2 = ldw2;
+    RowGemmArgs g;
+    SEI_REQUIRE(bias2 && D16 && sei_rowgemm_dgelu_bf16_eligible(M, N, K));
+    SEI_REQUIRE(rg_fill_operands(g, A, lda, W, ldw, M, K) == SEI_OK && rg_operands_ok(A2, lda2, W2, ldw2, K));
+    SEI_REQUIRE(((uintptr_t)D16 & 15) == 0 && nv > 0 && nv <= N && ld16 >= N && ld16 % 8 == 0);
+    g.A2 = A2; g.W2 = W2; g.lda2 = lda2; g.ldw2 = ldw2;
     g.bias = bias2; g.D16 = D16; g.ld16 = ld16; g.nv = nv;
     return rg_launch<3, 24, 32, 8, 1, RG_EPI_DGELU2, true>(g, (int)M, (hipStream_t)stream);
 }
@@ -1129,12 +1137,11 @@ extern "C" int sei_rowgemm_ln_bf16(const uint16_t *A, int lda, const uint16_t *W
                                    const float *bias, const float *row_scale, const float *res, float *out, const float *gamma,
                                    const float *beta, float eps, int ones_col, uint16_t *h16, int ldh, float *mean,
                                    float *rstd, void *stream) {
-    SEI_REQUIRE(A && W && bias && res && out && gamma && beta && h16 && mean && rstd && sei_rowgemm_ln_bf16_eligible(M, K, C));
-    SEI_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 && (((uintptr_t)A | (uintptr_t)W) & 15) == 0);
-    SEI_REQUIRE((unsigned long long)64 * (size_t)lda * 2 < (1ull << 32));
+    RowGemmArgs g;
+    SEI_REQUIRE(bias && res && out && gamma && beta && h16 && mean && rstd && sei_rowgemm_ln_bf16_eligible(M, K, C));
+    SEI_REQUIRE(rg_fill_operands(g, A, lda, W, ldw, M, K) == SEI_OK);
     SEI_REQUIRE((((uintptr_t)res | (uintptr_t)out) & 15) == 0 && ((uintptr_t)h16 & 7) == 0 && ldh >= 192 && ldh % 4 == 0);
-    RowGemmArgs g = {};
-    g.A = A; g.W = W; g.lda = lda; g.ldw = ldw; g.bias = bias; g.ldr = C; g.D32 = out; g.ld32 = C; g.D16 = h16; g.ld16 = ldh;
+    g.bias = bias; g.ldr = C; g.D32 = out; g.ld32 = C; g.D16 = h16; g.ld16 = ldh;
     g.nv = C; g.gamma = gamma; g.beta2 = beta; g.mean_out = mean; g.rstd_out = rstd; g.eps = eps; g.ones_col = ones_col;
     hipStream_t s = (hipStream_t)stream;
     const int m = (int)M;
@@ -1143,18 +1150,18 @@ extern "C" int sei_rowgemm_ln_bf16(const uint16_t *A, int lda, const uint16_t *W
         return K == 192 ? rg_launch<3, 12, 32, 4, 2, RG_EPI_SCALE_RES_LN, false>(g, m, s)
                         : rg_launch<6, 12, 32, 4, 2, RG_EPI_SCALE_RES_LN, false>(g, m, s);
     }
-    g.R1 = res; g.R2 = nullptr;
+    g.R1 = res;
     return K == 192 ? rg_launch<3, 12, 32, 4, 2, RG_EPI_RES_LN, false>(g, m, s)
                     : rg_launch<6, 12, 32, 4, 2, RG_EPI_RES_LN, false>(g, m, s);
 }
 
 extern "C" int sei_rowgemm_gelu_bf16(const uint16_t *A, int lda, const uint16_t *W, int ldw, const float *bias, int nv,
                                      uint16_t *D16, int ld16, long long M, int N, int K, int one_at, void *stream) {
-    SEI_REQUIRE(A && W && bias && D16 && sei_rowgemm_bf16_eligible(M, N, K, SEI_EPI_BIAS_GELU, 0));
-    SEI_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 && (((uintptr_t)A | (uintptr_t)W) & 15) == 0);
+    RowGemmArgs g;
+    SEI_REQUIRE(bias && D16 && sei_rowgemm_bf16_eligible(M, N, K, SEI_EPI_BIAS_GELU, 0));
+    SEI_REQUIRE(rg_fill_operands(g, A, lda, W, ldw, M, K) == SEI_OK);
     SEI_REQUIRE(nv == N && ld16 >= N && ld16 % 8 == 0 && ((uintptr_t)D16 & 15) == 0);       // bias: all N entries (zeros in the pad)
-    SEI_REQUIRE((unsigned long long)64 * (size_t)lda * 2 < (1ull << 32) && one_at >= -1 && one_at < N);
-    RowGemmArgs g = {};
-    g.A = A; g.W = W; g.lda = lda; g.ldw = ldw; g.bias = bias; g.D16 = D16; g.ld16 = ld16; g.nv = nv; g.gelu_one_at = one_at;
+    SEI_REQUIRE(one_at >= -1 && one_at < N);
+    g.bias = bias; g.D16 = D16; g.ld16 = ld16; g.nv = nv; g.gelu_one_at = one_at;
     return rg_launch<3, 24, 32, 8, 1, RG_EPI_GELU16, true>(g, (int)M, (hipStream_t)stream, 2);
 }
