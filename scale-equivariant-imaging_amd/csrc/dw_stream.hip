@@ -23,19 +23,13 @@
 //
 // The end is float atomics into the gradient (which therefore must be zeroed, not stored, at the start of a step):
 // every workgroup adds its partial block; the job table keeps their number per gradient near 256 / jobs.
-#include "sei_common.h"
+// The LDS image, its swizzle, the DMA piece offsets, the ring protocol and the fragment reads: rm_image.h, shared with
+// token_gemm.hip's tokgrad kernels.
+#include "rm_image.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-
-// 16-B chunk swizzle of a [64 rows][64 columns] bf16 image (128-B rows): as token_gemm.hip / gemm_bf16pq.h
-__device__ __forceinline__ int ds_swz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
-
 constexpr int DS_NT = 256;
-constexpr int DS_IMG = 64 * 128;
-constexpr int DS_NSTAGE = 3;
 constexpr int DS_MAX_UNITS = 40;
 
 struct DwUnit {                    // one block of one gradient
@@ -60,7 +54,7 @@ struct DwArgs {
 template <int PI, int QI, bool SWAP, bool PAIR>
 __device__ __forceinline__ void dw_stream_body(const DwUnit &u, int worker, int workers, char *smem) {
     constexpr int NIMG = PI + QI;
-    constexpr int STAGE = NIMG * DS_IMG;
+    constexpr int STAGE = NIMG * RM_IMG;
     constexpr int NPW = 2 * NIMG;                  // 1-KiB DMA pieces per wave and stage
     constexpr int PB = 2 * PI, QB = 2 * QI;        // 16-column blocks of a wave's share (the block is cut 2 x 2)
     const int lane = threadIdx.x & 63;
@@ -73,56 +67,14 @@ __device__ __forceinline__ void dw_stream_body(const DwUnit &u, int worker, int 
     if (nt <= 0) return;                                           // block-uniform, before any barrier
     const unsigned short *P1 = u.P1, *P2 = u.P2, *Q1 = u.Q1, *Q2 = u.Q2;
     const int ldp = u.ldp, ldq = u.ldq, kt_seg = u.kt_seg;
-
-    // ---- DMA: piece q = wave + 4 e of a stage: image q / 8 (the first PI: P), rows 8 (q % 8) .. + 7
     unsigned off[NPW];
-#pragma unroll
-    for (int e = 0; e < NPW; ++e) {
-        const int q = wave + 4 * e, im = q >> 3, p = q & 7;
-        const int krow = 8 * p + (lane >> 3);
-        const int ch = (lane & 7) ^ ds_swz(krow);
-        off[e] = im < PI ? ((unsigned)krow * (unsigned)ldp + (unsigned)(im * 64 + 8 * ch)) * 2u
-                         : ((unsigned)krow * (unsigned)ldq + (unsigned)(u.q0 + (im - PI) * 64 + 8 * ch)) * 2u;
-    }
-    auto issue = [&](int t) {                                       // k-tile t of this range (clamped: see the loop)
-        const int kt = kt0 + min(t, nt - 1);
-        const char *pb, *qb;
-        if (kt < kt_seg) {
-            pb = reinterpret_cast<const char *>(P1 + (size_t)kt * 64 * ldp);
-            qb = reinterpret_cast<const char *>(Q1 + (size_t)kt * 64 * ldq);
-        } else {
-            pb = reinterpret_cast<const char *>(P2 + (size_t)(kt - kt_seg) * 64 * ldp);
-            qb = reinterpret_cast<const char *>(Q2 + (size_t)(kt - kt_seg) * 64 * ldq);
-        }
-        char *dst = smem + (t % DS_NSTAGE) * STAGE;
-#pragma unroll
-        for (int e = 0; e < NPW; ++e) {
-            const int q = wave + 4 * e;                             // wave-uniform
-            // (inline-asm DMA: with the builtin the compiler drains vmcnt before every transposing read below -- the ring
-            // never had more than the current stage in flight; sei_common.h)
-            dma16_base((q >> 3) < PI ? pb : qb, off[e], dst + q * 1024);
-        }
-    };
-
-    // ---- fragments: 8 rows (32 ks + 8 lg + j) of column l16 of a 16-column block, two transposing reads
-    const int tq = l16 >> 2, tp = l16 & 3;
-    const int rm_lane = 128 * (8 * lg + tq) + 16 * ((tp >> 1) ^ ds_swz(8 * lg + tq)) + 8 * (tp & 1);
-    auto frag = [&](const char *img, int blk, int ks) -> bf16x8 {
-        const int base = rm_lane ^ (32 * blk);
-        const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * 32 * ks));
-        const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * (32 * ks + 4)));
-        return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
+    rm_stage_offsets<4, PI>(off, wave, lane, ldp, 0, ldq, u.q0);
+    const RmReader rd(l16, lg);
 
     // acc[a][b]: a walks the MFMA's A operand (P, or Q when SWAP), b its B operand
     constexpr int AB = SWAP ? QB : PB, BB = SWAP ? PB : QB;
     f32x4 acc[AB][BB];
-#pragma unroll
-    for (int a = 0; a < AB; ++a)
-#pragma unroll
-        for (int b = 0; b < BB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    rm_zero(acc);
     const bool works = !PAIR || wr == wc;                           // PAIR: the diagonal quadrants only (wave-uniform)
     // Bias gradient = the column sums of gy = gy^T 1: one more MFMA per A fragment against a fragment of ones (gy is the
     // MFMA's A operand in both orientations). Of the waves that hold the same gy tiles only one keeps the sums.
@@ -134,35 +86,30 @@ __device__ __forceinline__ void dw_stream_body(const DwUnit &u, int worker, int 
 #pragma unroll
     for (int a = 0; a < AB; ++a) accb[a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // Every iteration issues one stage (past the end: the last k-tile again, into a stage nobody reads), so the counted
-    // wait below always leaves exactly the NPW pieces of the next stage in flight.
-    issue(0);
-    issue(1);
+    auto issue = [&](int t, int stage) {                            // k-tile t of this range
+        const char *pb, *qb;
+        rm_ktile_bases(P1, P2, ldp, Q1, Q2, ldq, kt_seg, kt0 + t, pb, qb);
+        rm_stage_issue<4, PI>(pb, qb, off, wave, smem + stage * STAGE);
+    };
+    rm_ring_start(nt, issue);
     for (int t = 0; t < nt; ++t) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW) : "memory");  // this wave's pieces of stage t have landed
-        __builtin_amdgcn_s_barrier();                               // ... everyone's; and stage t - 1 is read out
-        issue(t + 2);
+        const char *st = smem + rm_ring_turn<NPW>(t, nt, issue) * STAGE;
         if (!works) continue;
-        const char *st = smem + (t % DS_NSTAGE) * STAGE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 fp[PB], fq[QB];
 #pragma unroll
             for (int i = 0; i < PB; ++i) {
                 const int bi = PB * wr + i;
-                fp[i] = frag(st + (bi >> 2) * DS_IMG, bi & 3, ks);
+                fp[i] = rd.frag(st + (bi >> 2) * RM_IMG, bi & 3, ks);
             }
 #pragma unroll
             for (int j = 0; j < QB; ++j) {
                 const int bj = QB * wc + j;
-                fq[j] = frag(st + (PI + (bj >> 2)) * DS_IMG, bj & 3, ks);
+                fq[j] = rd.frag(st + (PI + (bj >> 2)) * RM_IMG, bj & 3, ks);
             }
-#pragma unroll
-            for (int a = 0; a < AB; ++a)
-#pragma unroll
-                for (int b = 0; b < BB; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(SWAP ? fq[a] : fp[a], SWAP ? fp[b] : fq[b],
-                                                                        acc[a][b], 0, 0, 0);
+            if constexpr (SWAP) rm_mfma_block(acc, fq, fp);
+            else rm_mfma_block(acc, fp, fq);
             if (sums) {                                             // wave-uniform
 #pragma unroll
                 for (int a = 0; a < AB; ++a)
@@ -170,7 +117,7 @@ __device__ __forceinline__ void dw_stream_body(const DwUnit &u, int worker, int 
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the two clamped stages still in flight
+    sei_wait_vmcnt<0>();
     if (!works) return;
 
     // ---- float atomics: accumulator element (row 16 a + 4 lg + r, column 16 b + l16). Index of the wave's share inside
@@ -178,14 +125,8 @@ __device__ __forceinline__ void dw_stream_body(const DwUnit &u, int worker, int 
     // elements (pixel 2r's and pixel 2r + 1's contributions), hence offset 0.
     const int p_base = PAIR ? 0 : 32 * PI * wr, q_base = PAIR ? 0 : 32 * QI * wc;
     // gradient element of (p, q): not SWAP: D[p][q] (P = gy: rows); SWAP: D[q][p] (Q = gy)
-    float *d = SWAP ? u.D + (size_t)(q_base + 4 * lg) * u.ldd + p_base + l16
-                    : u.D + (size_t)(p_base + 4 * lg) * u.ldd + q_base + l16;
-#pragma unroll
-    for (int a = 0; a < AB; ++a)
-#pragma unroll
-        for (int b = 0; b < BB; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(d + (size_t)(16 * a + r) * u.ldd + 16 * b, acc[a][b][r]);
+    rm_atomic_out(SWAP ? u.D + (size_t)(q_base + 4 * lg) * u.ldd + p_base + l16
+                       : u.D + (size_t)(p_base + 4 * lg) * u.ldd + q_base + l16, u.ldd, acc);
     if (sums && l16 == 0) {                                         // every column of accb holds the same sums
         float *bp = u.bias + (SWAP ? q_base : p_base) + 4 * lg;
 #pragma unroll
@@ -199,7 +140,7 @@ __device__ __forceinline__ void dw_stream_body(const DwUnit &u, int worker, int 
 // a unit's pixel range per workgroup grows -- and its partial blocks (the float atomics at the end) shrink -- with the
 // number of units, and the atomics of one workgroup run under the streaming of the others.
 __global__ __launch_bounds__(DS_NT) void dw_stream_kernel(DwArgs g) {
-    __shared__ __attribute__((aligned(1024))) char smem[DS_NSTAGE * 6 * DS_IMG];
+    __shared__ __attribute__((aligned(1024))) char smem[3 * 6 * RM_IMG];
     int ui = 0;
     for (int k = 1; k < g.nunits; ++k)
         if ((int)blockIdx.x >= g.u[k].first) ui = k;               // uniform: scalar compares on the argument block

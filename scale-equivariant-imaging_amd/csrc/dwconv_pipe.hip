@@ -21,9 +21,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-
 __device__ __attribute__((aligned(16))) float g_dp_zero_chunk[4] = {0.f, 0.f, 0.f, 0.f};
 
 constexpr int DP_THREADS = 256;

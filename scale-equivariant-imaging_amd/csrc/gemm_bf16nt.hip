@@ -13,7 +13,7 @@
 //   * HBM/L2 -> LDS by global_load_lds_dwordx4: each wave-instruction ("piece") moves 1 KiB of full lines, no
 //     VGPR staging. K-contiguous operand: LDS image [row][128 B], 16-byte chunk c of row r at chunk position
 //     c ^ ((r>>1)&7), fragment = one ds_read_b128. Reduction-major operand: image [64 k-rows][256 B = 128
-//     columns], chunk swizzle swz_rmajor(row), fragment = two ds_read_b64_tr_b16 (the transposing LDS read).
+//     columns], chunk swizzle swz_rmajor(row) (rm_image.h), fragment = two ds_read_b64_tr_b16 (the transposing LDS read).
 //     Because the DMA destination is lane-linear, each swizzle is applied to the per-lane SOURCE address and
 //     again on the fragment read; SQ_LDS_BANK_CONFLICT = 0 on every variant.
 //   * double-buffered LDS, one barrier per k-tile (NSTAGE = 2); NSTAGE > 2 = ring with counted vmcnt and raw
@@ -23,12 +23,9 @@
 //   * gemm_bf16pp.h: an opt-in 256x256 ping-pong schedule on the same LDS images.
 //
 // Requirements checked by the host entries: K % 8 == 0, leading dimensions % 8 == 0, 16-byte aligned A and B.
-#include "sei_common.h"
+#include "rm_image.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
 
 constexpr int BK = 64;
 constexpr int ROW_BYTES = 128;
@@ -131,9 +128,7 @@ __device__ __forceinline__ void stage_tile(const unsigned short *__restrict__ G,
 
 // ---- operand stored reduction-major: element (o, k) at G[k*ld + o]; LDS image [64 k-rows][256 B = 128 o],
 // 16-byte chunk ch of row r at chunk position ch ^ swz(r) (cdna_hip_programming.md T10, image (b)); consumed
-// with ds_read_b64_tr_b16. Rows past K and chunks past the o edge are fed from the zero chunk.
-__device__ __forceinline__ int swz_rmajor(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-
+// with ds_read_b64_tr_b16. Rows past K and chunks past the o edge are fed from the zero chunk. (swz_rmajor: rm_image.h)
 __device__ __forceinline__ void stage_piece_rmajor(const unsigned short *__restrict__ G,
                                                    const unsigned short *__restrict__ G2, int k_seg, int ld, int o0,
                                                    int o_lim, int k0, int k_lim, char *lds_tile, int q, int lane) {

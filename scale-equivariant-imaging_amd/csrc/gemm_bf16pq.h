@@ -57,8 +57,7 @@ struct PqGeom {
 
 // 16-B chunk swizzle of a reduction-major half-tile ([64 k-rows][128 or 64 columns]): the fragment reads of 32
 // lanes (ds_read_b64_tr_b16: k-rows 8 lg + q, two neighbouring chunks each) fall on 16 different chunk slots of
-// the 256-B bank row. 256-B rows: swz_rmajor (gemm_bf16nt.hip); 128-B rows (two per bank row): below.
-__device__ __forceinline__ int pq_swz_rm128(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
+// the 256-B bank row. 256-B rows: swz_rmajor; 128-B rows (two per bank row): rm_swz128 (both, and why: rm_image.h).
 
 // BRM: B stored reduction-major (element (n, k) at B[k * ldb + n]: the weight as the forward pass stores it, used
 // by the data gradient). Its half-tiles are [64 k-rows][columns of the quadrant] images read with
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
     auto rm_piece = [&](int p, int pitch, int &krow, int &ch) {
         const int cpr = pitch / 16;
         krow = (64 / cpr) * p + lane / cpr;
-        ch = (lane % cpr) ^ (pitch == 256 ? swz_rmajor(krow) : pq_swz_rm128(krow));
+        ch = (lane % cpr) ^ (pitch == 256 ? swz_rmajor(krow) : rm_swz128(krow));
     };
     auto a_col = [&](int p, int q, int &krow) -> int {        // ARM: first of this lane's 8 rows of D, from m0
         int ch;
@@ -289,7 +288,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16pq_kernel(NtArgs g) {
     // half-tile: address = tile + (lane_off ^ 32 blk [^ 16]) + pitch * (32 ks [+ 4]), the last term an immediate.
     const int tq = l16 >> 2, tp = l16 & 3;
     const int rm_lane256 = 256 * (8 * lg + tq) + 16 * ((tp >> 1) ^ ((tq << 2) | ((2 * lg) & 3))) + 8 * (tp & 1);
-    const int rm_lane128 = 128 * (8 * lg + tq) + 16 * ((tp >> 1) ^ pq_swz_rm128(8 * lg + tq)) + 8 * (tp & 1);
+    const int rm_lane128 = 128 * (8 * lg + tq) + 16 * ((tp >> 1) ^ rm_swz128(8 * lg + tq)) + 8 * (tp & 1);   // = rm_lane_of(l16, lg)
     auto frag_rm = [&](const char *t, int pitch, int blk, int ks) -> bf16x8 {   // 16-column block blk of the half
         const int base = (pitch == 256 ? rm_lane256 : rm_lane128) ^ (32 * blk);
         const int base_hi = pitch == 256 ? base ^ 16 : base;

@@ -26,9 +26,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-
 constexpr int WAVES = 9, NT = 64 * WAVES, PX = 16 * WAVES;   // 144 pixels per workgroup
 constexpr int NSTAGE = 4;
 // Per width C (32 or 128): 4 C hidden units in slices of 32; a slice image is 32 x C or C x 32 bf16 = C / 16 pieces of 1 KiB.

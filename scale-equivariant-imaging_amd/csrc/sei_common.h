@@ -8,6 +8,10 @@
 
 #define SEI_WAVE 64
 
+// LDS / global pointers as __builtin_amdgcn_global_load_lds takes them
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(1))) const void glb_void;
+
 #define SEI_REQUIRE(cond) \
     do {                  \
         if (!(cond)) return SEI_ERR_BAD_ARG; \

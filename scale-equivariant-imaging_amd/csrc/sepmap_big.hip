@@ -19,11 +19,10 @@
 // [64 k][64 n] bf16 images (float32 is converted on the way), reads it back with the transposing LDS read as the MFMA's A
 // operand -- so a lane's accumulator holds FOUR CONSECUTIVE n of one output row: 8- / 16-byte stores -- and prefetches the
 // next item's block into registers under the MFMAs. x is read once, T written and read once, y written once.
-#include "sei_common.h"
+// (The image, its chunk swizzle and the fragment read are rm_image.h's, as in the streamed weight-gradient kernels.)
+#include "rm_image.h"
 
 namespace {
-
-__device__ __forceinline__ int sb_swz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
 
 struct CmatArgs {
     const void *X;              // (batch, K, N) float32 (IN32) or bf16
@@ -39,7 +38,7 @@ struct CmatArgs {
 template <int KS, int MTW, bool IN32, bool OUT16>
 __global__ __launch_bounds__(512) void cmat_gemm_kernel(CmatArgs g) {
     constexpr int NIMG = (KS + 1) / 2;                              // [64 k][64 n] images per buffer
-    constexpr int BUF = NIMG * 8192;
+    constexpr int BUF = NIMG * RM_IMG;
     __shared__ __attribute__((aligned(1024))) char smem[2 * BUF];
     const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, lg = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = blockDim.x >> 6, nthreads = blockDim.x;
@@ -85,31 +84,22 @@ __global__ __launch_bounds__(512) void cmat_gemm_kernel(CmatArgs g) {
             const int p = tid + e * nthreads;
             const int k = p / PPR, c = p % PPR;
             if (k >= KS * 32) continue;
-            char *row = buf + (k >> 6) * 8192 + (k & 63) * 128;
+            char *row = buf + (k >> 6) * RM_IMG + (k & 63) * 128;
             if constexpr (IN32) {
-                const int ch = (c >> 1) ^ sb_swz(k & 63);           // 16-byte chunk = 8 bf16 = two pieces
+                const int ch = (c >> 1) ^ rm_swz128(k & 63);           // 16-byte chunk = 8 bf16 = two pieces
                 const f32x4 v = __builtin_bit_cast(f32x4, pre[e]);
                 bf16x4 o;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) o[q] = (__bf16)v[q];
                 *reinterpret_cast<bf16x4 *>(row + ch * 16 + (c & 1) * 8) = o;
             } else {
-                const int ch = c ^ sb_swz(k & 63);
+                const int ch = c ^ rm_swz128(k & 63);
                 *reinterpret_cast<uint4 *>(row + ch * 16) = pre[e];
             }
         }
     };
     // ---- fragments of X^T: 8 k (32 ks + 8 lg + j) of column l16 of 16-column block blk
-    const int tq = l16 >> 2, tp = l16 & 3;
-    const int rm_lane = 128 * (8 * lg + tq) + 16 * ((tp >> 1) ^ sb_swz(8 * lg + tq)) + 8 * (tp & 1);
-    auto frag = [&](const char *img, int blk, int ks) -> bf16x8 {
-        const int base = rm_lane ^ (32 * blk);
-        const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * 32 * ks));
-        const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * (32 * ks + 4)));
-        return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
+    const RmReader rd(l16, lg);
 
     // ---- A fragments of this wave, per m-group (reloaded when the group changes: L2 hits, a few KB)
     bf16x8 ah[MTW][KS], al[MTW][KS];
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(512) void cmat_gemm_kernel(CmatArgs g) {
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 fx[4];
 #pragma unroll
-            for (int nb = 0; nb < 4; ++nb) fx[nb] = frag(buf + (ks >> 1) * 8192, nb, ks & 1);
+            for (int nb = 0; nb < 4; ++nb) fx[nb] = rd.frag(buf + (ks >> 1) * RM_IMG, nb, ks & 1);
 #pragma unroll
             for (int t = 0; t < MTW; ++t)
 #pragma unroll

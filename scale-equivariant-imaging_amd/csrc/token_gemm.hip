@@ -14,25 +14,24 @@
 //                      reads, 83 B of LDS per clock against 188 for the 64 x 32 wave tiles of the 128 x 128 loop,
 //                      which that loop's 520 TFLOP/s were bound by) and a contiguous range of tokens; blocks of the
 //                      same token range sit on the same XCD, so X crosses the fabric once. Float atomics at the end.
+//                      (The token-major LDS image and everything that fills and reads it: rm_image.h.)
 //   sei_rowgemm_bf16   D = epilogue(A W^T), the layer's matrix in registers, row tiles streamed (described further down)
 //     .._ln_bf16       + the LayerNorm BEHIND a residual layer in that layer's epilogue (proj -> norm2, fc2 -> next norm1)
 //     .._lnbwd_bf16    + LayerNorm BACKWARD (+ residual gradient, bf16 copy, column sums) behind a data gradient
 //     .._dgelu_bf16    fc2's data gradient with the GELU' input recomputed by a second product in registers
 //     .._gelu_bf16     fc1's forward, bf16 output only, with a ones column that carries fc2's bias gradient
-#include "sei_common.h"
+#include "rm_image.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-
-// 16-B chunk swizzle of a [64 tokens][64 columns] image (128-B rows, two per 256-B bank row): as gemm_bf16pq.h
-__device__ __forceinline__ int tg_swz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
-
-constexpr int TG_NT = 256;                 // four waves, one per SIMD: 144 accumulator registers each (NW = 4)
-constexpr int TG_IMG = 64 * 128;           // one [64 tokens][64 columns] bf16 image
-constexpr int TG_STAGE = 6 * TG_IMG;       // 192 columns of dY + 192 columns of X
-constexpr int TG_NSTAGE = 3;
+// Eight waves of 96 x 48, two per SIMD (72 accumulator registers each): one wave's fragment reads under the other's MFMAs.
+// (Against four waves of 96 x 96 each stage is read 1.5 x as often from LDS, which has the room: that loop was bound by the
+// read -> wait -> MFMA sequence of its single wave per SIMD, not by LDS bandwidth.)
+constexpr int TG_NW = 8, TG_NT = 64 * TG_NW;
+constexpr int TG_WCN = 4;                                  // 2 row groups x 4 column groups of waves
+constexpr int TG_RB = 6, TG_CB = 3;                        // 16-row / 16-column blocks per wave
+constexpr int TG_NPIECE = 48 / TG_NW;                      // 1-KiB DMA pieces per wave and stage
+constexpr int TG_STAGE = 6 * RM_IMG;                       // 192 columns of dY (images 0-2) + 192 columns of X (3-5)
 constexpr int TG_MAX_BLOCKS = SEI_TOKGRAD_MAX_BLOCKS;
 
 struct TokGradArgs {
@@ -42,169 +41,99 @@ struct TokGradArgs {
     int workers_per_xcd;      // token ranges per XCD (each served by `nblk` workgroups of that XCD)
 };
 
-// NW = 4: four waves of 96 x 96; NW = 8: eight waves of 96 x 48, two per SIMD -- one wave's fragment reads under the
-// other's MFMAs (each stage is read 1.5 x as often from LDS, which has the room: the loop was bound by the read -> wait ->
-// MFMA sequence of its single wave per SIMD, not by LDS bandwidth)
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void tokgrad_kernel(TokGradArgs g) {
-    constexpr int WRN = NW == 16 ? 4 : 2, WCN = NW / WRN;            // row groups x column groups of waves
-    constexpr int RBk = 12 / WRN, CB = 12 / WCN, NPIECE = 48 / NW;   // 16-row / 16-column blocks per wave, DMA pieces per wave
-    __shared__ __attribute__((aligned(1024))) char smem[TG_NSTAGE * TG_STAGE];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wr = wave / WCN, wc = wave % WCN;
-    const int l16 = lane & 15, lg = lane >> 4;
-
-    // workgroups are dealt round-robin to the XCDs: slot s of XCD x = token range (s / nblk) * 8 + x, block s % nblk --
-    // the blocks of a token range (the three 192-row blocks of a qkv gradient share X) go through the same L2
+// Workgroups are dealt round-robin to the XCDs: slot s of XCD x = token range (s / nblk) * 8 + x, block s % nblk -- the
+// blocks of a token range (the three 192-row blocks of a qkv gradient share X) go through the same L2. This workgroup's
+// block and its k-tiles [kt0, kt0 + nt); nt <= 0: nothing to do (block-uniform: return before any barrier).
+struct TgRange {
+    int bsel, kt0, nt;
+};
+__device__ __forceinline__ TgRange tg_range(const TokGradArgs &g) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int wslot = slot / g.nblk, bsel = slot - wslot * g.nblk;
-    if (wslot >= g.workers_per_xcd) return;
+    if (wslot >= g.workers_per_xcd) return {0, 0, 0};
     const int worker = wslot * 8 + xcd, workers = 8 * g.workers_per_xcd;
     const int kt0 = (int)((long long)g.kt_total * worker / workers);
     const int kt1 = (int)((long long)g.kt_total * (worker + 1) / workers);
-    const int nt = kt1 - kt0;
-    if (nt <= 0) return;                                           // block-uniform, before any barrier
+    return {bsel, kt0, kt1 - kt0};
+}
+
+// The MFMAs of one stage: this wave's 6 x 3 blocks over the stage's 64 tokens (a macro, not a function: both kernels'
+// register allocation follows the parent's only with this text in the loop body itself)
+#define TG_COMPUTE(st)                                                                                          \
+    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                          \
+        bf16x8 fa[TG_RB], fb[TG_CB];                                                                            \
+        _Pragma("unroll") for (int i = 0; i < TG_RB; ++i) {                                                     \
+            const int bi = TG_RB * wr + i;                                                                      \
+            fa[i] = rd.frag((st) + (bi >> 2) * RM_IMG, bi & 3, ks);                                             \
+        }                                                                                                       \
+        _Pragma("unroll") for (int j = 0; j < TG_CB; ++j) {                                                     \
+            const int bj = TG_CB * wc + j;                                                                      \
+            fb[j] = rd.frag((st) + (3 + (bj >> 2)) * RM_IMG, bj & 3, ks);                                       \
+        }                                                                                                       \
+        rm_mfma_block(acc, fa, fb);                                                                             \
+    }
+
+__global__ __launch_bounds__(TG_NT) void tokgrad_kernel(TokGradArgs g) {
+    __shared__ __attribute__((aligned(1024))) char smem[3 * TG_STAGE];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wr = wave / TG_WCN, wc = wave % TG_WCN;
+    const int l16 = lane & 15, lg = lane >> 4;
+    const TgRange rg = tg_range(g);
+    const int bsel = rg.bsel, kt0 = rg.kt0, nt = rg.nt;
+    if (nt <= 0) return;
     const SeiTokGradBlock &b = g.blk[bsel];                         // uniform index: scalar loads from the argument block
     const unsigned short *Y1 = b.Y1, *Y2 = b.Y2, *X1 = b.X1, *X2 = b.X2;
     const int ldy = b.ldy, ldx = b.ldx;
+    unsigned off[TG_NPIECE];
+    rm_stage_offsets<TG_NW, 3>(off, wave, lane, ldy, b.y0, ldx, b.x0);
+    const RmReader rd(l16, lg);
+    f32x4 acc[TG_RB][TG_CB];
+    rm_zero(acc);
 
-    // ---- DMA: 48 1-KiB pieces per stage, 48 / NW per wave; piece q = image q / 8 (0-2: dY, 3-5: X), rows 8 (q % 8) ..
-    unsigned off[NPIECE];
-#pragma unroll
-    for (int e = 0; e < NPIECE; ++e) {
-        const int q = wave + NW * e, im = q >> 3, p = q & 7;
-        const int krow = 8 * p + (lane >> 3);
-        const int ch = (lane & 7) ^ tg_swz(krow);
-        off[e] = im < 3 ? ((unsigned)krow * (unsigned)ldy + (unsigned)(b.y0 + im * 64 + 8 * ch)) * 2u
-                        : ((unsigned)krow * (unsigned)ldx + (unsigned)(b.x0 + (im - 3) * 64 + 8 * ch)) * 2u;
-    }
-    auto issue = [&](int u) {                                       // k-tile u of this range (clamped: see the loop)
-        const int kt = kt0 + min(u, nt - 1);
+    auto issue = [&](int u, int stage) {                            // k-tile u of this range
         const char *yb, *xb;
-        if (kt < g.kt_seg) {
-            yb = reinterpret_cast<const char *>(Y1 + (size_t)kt * 64 * ldy);
-            xb = reinterpret_cast<const char *>(X1 + (size_t)kt * 64 * ldx);
-        } else {
-            yb = reinterpret_cast<const char *>(Y2 + (size_t)(kt - g.kt_seg) * 64 * ldy);
-            xb = reinterpret_cast<const char *>(X2 + (size_t)(kt - g.kt_seg) * 64 * ldx);
-        }
-        char *dst = smem + (u % TG_NSTAGE) * TG_STAGE;
-#pragma unroll
-        for (int e = 0; e < NPIECE; ++e) {
-            const int q = wave + NW * e;                            // wave-uniform
-            dma16_base((q >> 3) < 3 ? yb : xb, off[e], dst + q * 1024);      // (inline asm: sei_common.h)
-        }
+        rm_ktile_bases(Y1, Y2, ldy, X1, X2, ldx, g.kt_seg, kt0 + u, yb, xb);
+        rm_stage_issue<TG_NW, 3>(yb, xb, off, wave, smem + stage * TG_STAGE);
     };
-
-    // ---- fragments: 8 tokens (32 ks + 8 lg + j) of column l16 of a 16-column block, two transposing reads
-    const int tq = l16 >> 2, tp = l16 & 3;
-    const int rm_lane = 128 * (8 * lg + tq) + 16 * ((tp >> 1) ^ tg_swz(8 * lg + tq)) + 8 * (tp & 1);
-    auto frag = [&](const char *img, int blk, int ks) -> bf16x8 {
-        const int base = rm_lane ^ (32 * blk);
-        const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * 32 * ks));
-        const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * (32 * ks + 4)));
-        return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
-
-    f32x4 acc[RBk][CB];
-#pragma unroll
-    for (int i = 0; i < RBk; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // Every iteration issues one stage (past the end: the last k-tile again, into a stage nobody reads), so the
-    // counted wait below always leaves exactly the pieces of the next stage (12 or 6 per wave) in flight.
-    issue(0);
-    issue(1);
-    for (int u = 0; u < nt; ++u) {
-        if constexpr (NW == 4) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");   // this wave's pieces of stage u have landed
-        else if constexpr (NW == 8) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                               // ... everyone's; and stage u - 1 is read out
-        issue(u + 2);
-        const char *st = smem + (u % TG_NSTAGE) * TG_STAGE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 fa[RBk], fb[CB];
-#pragma unroll
-            for (int i = 0; i < RBk; ++i) {
-                const int bi = RBk * wr + i;
-                fa[i] = frag(st + (bi >> 2) * TG_IMG, bi & 3, ks);
-            }
-#pragma unroll
-            for (int j = 0; j < CB; ++j) {
-                const int bj = CB * wc + j;
-                fb[j] = frag(st + (3 + (bj >> 2)) * TG_IMG, bj & 3, ks);
-            }
-#pragma unroll
-            for (int i = 0; i < RBk; ++i)
-#pragma unroll
-                for (int j = 0; j < CB; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
+    rm_ring_start(nt, issue);
+    for (int t = 0; t < nt; ++t) {
+        const char *st = smem + rm_ring_turn<TG_NPIECE>(t, nt, issue) * TG_STAGE;
+        TG_COMPUTE(st)
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the two clamped stages still in flight
-
-    // ---- float atomics: accumulator element (row 4 lg + r, column l16) of block (i, j). One atomic per clock and L2
-    // channel is what they cost (measured: 27 us for the 256 x 147 KB of a launch, whatever the scope or the number of
-    // adders per address), which is why a launch should carry as many 192 x 192 blocks as it can: the token range of a
-    // workgroup grows and the number of partial blocks per output shrinks with the block count.
-    float *d = b.D + (size_t)(16 * RBk * wr + 4 * lg) * b.ldd + 16 * CB * wc + l16;
-#pragma unroll
-    for (int i = 0; i < RBk; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(d + (size_t)(16 * i + r) * b.ldd + 16 * j, acc[i][j][r]);
+    sei_wait_vmcnt<0>();
+    // One atomic per clock and L2 channel is what the write-out costs (measured: 27 us for the 256 x 147 KB of a launch,
+    // whatever the scope or the number of adders per address), which is why a launch should carry as many 192 x 192
+    // blocks as it can: the token range of a workgroup grows and the number of partial blocks per output shrinks with
+    // the block count.
+    rm_atomic_out(b.D + (size_t)(16 * TG_RB * wr + 4 * lg) * b.ldd + 16 * TG_CB * wc + l16, b.ldd, acc);
 }
 
-// The same product with the token stages travelling through REGISTERS: eight waves of 96 x 48, every wave loads its six
-// 1-KiB pieces of a stage with plain 16-byte loads THREE stages ahead (3 x 24 registers per lane), writes them into one of
-// two LDS stages one iteration before they are read, and computes as above. What the LDS-DMA ring is short of is bytes
-// in flight: three 48-KB stages fill the LDS, one of them is being read, so 96 KB per CU are on their way -- 4.2 TB/s at the
-// ~6 us a loaded request takes, where the same ring with nothing to compute (every slot reissued at once) streams 6.0.
-// Registers have the room the LDS lacks: 144 KB per CU in flight.
-__global__ __launch_bounds__(512, 2) void tokgrad_regs_kernel(TokGradArgs g) {
-    constexpr int NW = 8, WCN = 4, RBk = 6, CB = 3, NPIECE = 6;
+// The same product with the token stages travelling through REGISTERS: every wave loads its six 1-KiB pieces of a stage
+// with plain 16-byte loads THREE stages ahead (3 x 24 registers per lane), writes them into one of two LDS stages one
+// iteration before they are read, and computes as above. What the LDS-DMA ring is short of is bytes in flight: three
+// 48-KB stages fill the LDS, one of them is being read, so 96 KB per CU are on their way -- 4.2 TB/s at the ~6 us a loaded
+// request takes, where the same ring with nothing to compute (every slot reissued at once) streams 6.0. Registers have
+// the room the LDS lacks: 144 KB per CU in flight.
+__global__ __launch_bounds__(TG_NT, 2) void tokgrad_regs_kernel(TokGradArgs g) {
+    constexpr int NW = TG_NW, NPIECE = TG_NPIECE;
     __shared__ __attribute__((aligned(1024))) char smem[2 * TG_STAGE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wr = wave / WCN, wc = wave % WCN;
+    const int wr = wave / TG_WCN, wc = wave % TG_WCN;
     const int l16 = lane & 15, lg = lane >> 4;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int wslot = slot / g.nblk, bsel = slot - wslot * g.nblk;
-    if (wslot >= g.workers_per_xcd) return;
-    const int worker = wslot * 8 + xcd, workers = 8 * g.workers_per_xcd;
-    const int kt0 = (int)((long long)g.kt_total * worker / workers);
-    const int kt1 = (int)((long long)g.kt_total * (worker + 1) / workers);
-    const int nt = kt1 - kt0;
+    const TgRange rg = tg_range(g);
+    const int bsel = rg.bsel, kt0 = rg.kt0, nt = rg.nt;
     if (nt <= 0) return;
     const SeiTokGradBlock &b = g.blk[bsel];
     const unsigned short *Y1 = b.Y1, *Y2 = b.Y2, *X1 = b.X1, *X2 = b.X2;
     const int ldy = b.ldy, ldx = b.ldx;
     unsigned off[NPIECE];
-#pragma unroll
-    for (int e = 0; e < NPIECE; ++e) {
-        const int q = wave + NW * e, im = q >> 3, p = q & 7;
-        const int krow = 8 * p + (lane >> 3);
-        const int ch = (lane & 7) ^ tg_swz(krow);
-        off[e] = im < 3 ? ((unsigned)krow * (unsigned)ldy + (unsigned)(b.y0 + im * 64 + 8 * ch)) * 2u
-                        : ((unsigned)krow * (unsigned)ldx + (unsigned)(b.x0 + (im - 3) * 64 + 8 * ch)) * 2u;
-    }
+    rm_stage_offsets<NW, 3>(off, wave, lane, ldy, b.y0, ldx, b.x0);
     // loads the compiler does not track (it would wait for all of them at the first use of any): counted waits below
     auto load = [&](int u, u32x4 (&r)[NPIECE]) {
-        const int kt = kt0 + min(u, nt - 1);
         const char *yb, *xb;
-        if (kt < g.kt_seg) {
-            yb = reinterpret_cast<const char *>(Y1 + (size_t)kt * 64 * ldy);
-            xb = reinterpret_cast<const char *>(X1 + (size_t)kt * 64 * ldx);
-        } else {
-            yb = reinterpret_cast<const char *>(Y2 + (size_t)(kt - g.kt_seg) * 64 * ldy);
-            xb = reinterpret_cast<const char *>(X2 + (size_t)(kt - g.kt_seg) * 64 * ldx);
-        }
+        rm_ktile_bases(Y1, Y2, ldy, X1, X2, ldx, g.kt_seg, kt0 + min(u, nt - 1), yb, xb);
 #pragma unroll
         for (int e = 0; e < NPIECE; ++e) {
             const int q = wave + NW * e;
@@ -220,42 +149,12 @@ __global__ __launch_bounds__(512, 2) void tokgrad_regs_kernel(TokGradArgs g) {
             *reinterpret_cast<u32x4 *>(dst + (wave + NW * e) * 1024) = r[e];
         }
     };
-    const int tq = l16 >> 2, tp = l16 & 3;
-    const int rm_lane = 128 * (8 * lg + tq) + 16 * ((tp >> 1) ^ tg_swz(8 * lg + tq)) + 8 * (tp & 1);
-    auto frag = [&](const char *img, int blk, int ks) -> bf16x8 {
-        const int base = rm_lane ^ (32 * blk);
-        const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * 32 * ks));
-        const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) v4s *)(img + base + 128 * (32 * ks + 4)));
-        return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
-    f32x4 acc[RBk][CB];
-#pragma unroll
-    for (int i = 0; i < RBk; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const RmReader rd(l16, lg);
+    f32x4 acc[TG_RB][TG_CB];
+    rm_zero(acc);
     auto compute = [&](int u) {
         const char *st = smem + (u & 1) * TG_STAGE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 fa[RBk], fb[CB];
-#pragma unroll
-            for (int i = 0; i < RBk; ++i) {
-                const int bi = RBk * wr + i;
-                fa[i] = frag(st + (bi >> 2) * TG_IMG, bi & 3, ks);
-            }
-#pragma unroll
-            for (int j = 0; j < CB; ++j) {
-                const int bj = CB * wc + j;
-                fb[j] = frag(st + (3 + (bj >> 2)) * TG_IMG, bj & 3, ks);
-            }
-#pragma unroll
-            for (int i = 0; i < RBk; ++i)
-#pragma unroll
-                for (int j = 0; j < CB; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
+        TG_COMPUTE(st)
     };
     // Stage u lives in register set u % 3 from three iterations before its turn until one before, then in LDS stage
     // u % 2. Iteration u: [stage u + 1 has landed: counted wait] [barrier: everyone is done reading LDS stage (u + 1) % 2
@@ -303,14 +202,9 @@ __global__ __launch_bounds__(512, 2) void tokgrad_regs_kernel(TokGradArgs g) {
 #undef TG_STEP
 #undef TG_TAIL
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    float *d = b.D + (size_t)(16 * RBk * wr + 4 * lg) * b.ldd + 16 * CB * wc + l16;
-#pragma unroll
-    for (int i = 0; i < RBk; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(d + (size_t)(16 * i + r) * b.ldd + 16 * j, acc[i][j][r]);
+    rm_atomic_out(b.D + (size_t)(16 * TG_RB * wr + 4 * lg) * b.ldd + 16 * TG_CB * wc + l16, b.ldd, acc);
 }
+#undef TG_COMPUTE
 
 // ---------------------------------------------------------------------------------------------------------------
 // sei_rowgemm_bf16: D (M x N) = epilogue(A (M x K) W^T), W (N x K) the layer's matrix, K = 192 / 384 / 576 and
@@ -993,10 +887,10 @@ extern "C" int sei_tokgrad_bf16_blocks(const SeiTokGradBlock *blocks, int nblock
     // Ranges of at least eight 64-token stages per workgroup: the stages travel through registers (three in flight);
     // shorter ones: the LDS-DMA ring with eight waves.
     if (g.kt_total / (8 * g.workers_per_xcd) >= 8)
-        hipLaunchKernelGGL(tokgrad_regs_kernel, dim3(8 * (unsigned)(g.workers_per_xcd * nblocks)), dim3(512), 0,
+        hipLaunchKernelGGL(tokgrad_regs_kernel, dim3(8 * (unsigned)(g.workers_per_xcd * nblocks)), dim3(TG_NT), 0,
                            (hipStream_t)stream, g);
     else
-        hipLaunchKernelGGL(tokgrad_kernel<8>, dim3(8 * (unsigned)(g.workers_per_xcd * nblocks)), dim3(2 * TG_NT), 0,
+        hipLaunchKernelGGL(tokgrad_kernel, dim3(8 * (unsigned)(g.workers_per_xcd * nblocks)), dim3(TG_NT), 0,
                            (hipStream_t)stream, g);
     return sei_launch_status();
 }

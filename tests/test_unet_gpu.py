@@ -1476,6 +1476,31 @@ def test_streamed_weight_gradients_of_the_shallow_levels(K1, K2):
     assert elig(512, 2048, 512, 2048, 128, 0) == 0 and elig(64, 256, 64, 256, 128, 0) == 0 and elig(128, 128, 128, 128, 128, 0) == 0
 
 
+def test_streamed_weight_gradients_of_a_table_longer_than_one_launch():
+    """sei_dwstream_bf16_jobs with more units than one launch holds (40): eleven jobs of (Mo, Ni) = (1024, 128) are four
+    256-row blocks each, 44 units, so the entry point launches the full table and then the rest. One k-tile per job
+    (K1 = 64, K2 = 0: the smallest the kernel takes), every job with its own operands, running gradient and bias
+    gradient, all in ONE call; each against the float32 product of the same bf16 operands on top of the running values,
+    under the bar of the test above."""
+    import _native as N
+    gen = torch.Generator(device="cuda").manual_seed(44)
+    Mo, Ni, K1 = 1024, 128, 64
+    assert N.lib().sei_dwstream_bf16_eligible(Mo, Ni, Mo, Ni, K1, 0) != 0
+    jobs, expect = [], []
+    for _ in range(11):
+        gy = (0.5 * torch.randn((K1, Mo), device="cuda", generator=gen)).bfloat16()
+        x = torch.randn((K1, Ni), device="cuda", generator=gen).bfloat16()
+        d = torch.randn((Mo, Ni), device="cuda", generator=gen)
+        bg = torch.randn(Mo, device="cuda", generator=gen)
+        expect.append((d, d + gy.float().T @ x.float(), bg, bg + gy.float().sum(0), gy, x))
+        jobs.append(N.DwStreamJob(gy.data_ptr(), gy.data_ptr(), x.data_ptr(), x.data_ptr(), Mo, Ni, Mo, Ni, d.data_ptr(), Ni, 0,
+                                  K1, 0, N.ptr(bg)))
+    N.call("sei_dwstream_bf16_jobs", (N.DwStreamJob * len(jobs))(*jobs), len(jobs))
+    for i, (d, ref, bg, bref, _, _) in enumerate(expect):
+        assert relerr(d, ref) < 2e-5, (i, relerr(d, ref))
+        assert relerr(bg, bref) < 2e-5, (i, relerr(bg, bref))
+
+
 def test_streamed_weight_gradients_inside_a_backward_pass(ops):
     """The U-Net's backward pass in bf16 mode with the shallow levels' weight gradients collected into one job table per
     block shape at the end of the pass (models/_wgrad.py: queue_dwstream) against the same pass on the tiled GEMMs
