@@ -972,6 +972,41 @@ size_t sei_rowgemm_ln_bf16_eligible(long long M, int K, int C);
 int sei_rowgemm_gelu_bf16(const uint16_t *A, int lda, const uint16_t *W, int ldw, const float *bias, int nv, uint16_t *D16,
                           int ld16, long long M, int N, int K, int one_at, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The DRUNet denoiser of the PlugAndPlay baseline (reference src/models/pnp.py -> deepinv's DRUNet, restated in
+ * models/drunet.py): bias-free 3x3 convolutions at 64 / 128 / 256 / 512 channels (anything else: SEI_ERR_BAD_ARG), bf16
+ * MFMA with float32 accumulation. Activations are bf16 channels-last on zero-bordered grids (B, H + 2, W + 2, C) with
+ * W + 3 guard rows of C elements in front and behind (sei_pad_nhwc_bf16's layout); every grid pointer below is ROW 0 of
+ * its grid (behind the guard rows). The residual trunk T is float32 with the same row indexing (no guard rows needed).
+ * Weights are bf16, tap-major and K-contiguous: (N, taps * Cin), tap t = ky * kw + kx. Only interior rows are written:
+ * the border of an output grid stays as the caller zeroed it, guard rows are read but never written and never reach a
+ * result. No split-K, no atomics: the same bits on every run and at every position in the batch. Pointers 16-byte
+ * aligned (x and the image of the tail: 4).
+ *   sei_drunet_conv3x3  epilogue 0: Y16 = bf16(relu(conv(X))) (T_* NULL) -- ResBlock conv 1;
+ *                       epilogue 1: T_out = T_in + conv(X) [+ T_skip], Y16 = bf16(T_out) -- ResBlock conv 2; T_out may be
+ *                       T_in. T_skip is the U-Net skip added ahead of an up block (or of the tail).
+ *   sei_drunet_down     nn.Conv2d(Cin, Cout, 2, 2): X is the (2 Ho, 2 Wo) grid, T_out / Y16 the (Ho, Wo) ones.
+ *   sei_drunet_up       nn.ConvTranspose2d(Cin, Cout, 2, 2) in one launch: Wt (4 Cout, Cin), row (ky * 2 + kx) Cout + co;
+ *                       X is the (H, W) grid, T_out / Y16 the (2 H, 2 W) ones.
+ *   sei_drunet_head     conv3x3(cat(x, sigma)) for x (B, 3, H, W) float32 NCHW: Wt (Cout, 9 * 32), the four input channels
+ *                       zero-padded to 32 (the constant channel is zero outside the image, so it is no bias); T_out and
+ *                       Y16 = bf16(T_out). work: sei_drunet_work_bytes(B, H, W) bytes (0 = arguments refused).
+ *   sei_drunet_tail     out (B, 3, H, W) float32 NCHW = conv3x3(X), Wt (16, 9 * Cin) with zero rows behind the third. */
+size_t sei_drunet_work_bytes(int B, int H, int W);
+int sei_drunet_conv3x3(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W, int epilogue,
+                       const float *T_in, const float *T_skip, float *T_out, uint16_t *Y16, void *stream);
+/* sei_drunet_conv3x3 with the tile chosen by the caller: a wave takes 16 pb grid rows x 64 channels, pb 1, 2 or 4, 0 = the
+ * default (by the number of waves the launch has); anything else is SEI_ERR_BAD_ARG. Same bits for every pb. */
+int sei_drunet_conv3x3_ex(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W, int epilogue,
+                          const float *T_in, const float *T_skip, float *T_out, uint16_t *Y16, int pb, void *stream);
+int sei_drunet_down(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int Ho, int Wo, float *T_out,
+                    uint16_t *Y16, void *stream);
+int sei_drunet_up(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W, float *T_out,
+                  uint16_t *Y16, void *stream);
+int sei_drunet_head(const float *x, float sigma, const uint16_t *Wt, int Cout, int B, int H, int W, float *T_out,
+                    uint16_t *Y16, void *work, void *stream);
+int sei_drunet_tail(const uint16_t *X, const uint16_t *Wt, int Cin, int B, int H, int W, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,12 @@ SIGNATURES = {
     "sei_adam_scalars_to_device": [_F, _F, _F, _F, _F, _I, _P, _P],
     "sei_sgd_fused": [_P, _P, _P, _P, _Z, _Z, _F, _F, _P, _P, _I, _P],
     "sei_sgd_penalty_finish": [_P, _Z, _P, _P],
+    "sei_drunet_conv3x3": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "sei_drunet_conv3x3_ex": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
+    "sei_drunet_down": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "sei_drunet_up": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "sei_drunet_head": [_P, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "sei_drunet_tail": [_P, _P, _I, _I, _I, _I, _P, _P],
 }
 
 _lib = None
@@ -217,6 +223,7 @@ SIZE_QUERIES = {
     "sei_sepmap2_small_eligible": [_I, _I, _I, _I, _I, _I],
     "sei_cast_bf16_colsum_parts_count": [_I, _I],
     "sei_sgd_partials": [_Z, _Z, _I],
+    "sei_drunet_work_bytes": [_I, _I, _I],
 }
 ABI_VERSION = 12      # SEI_ABI_VERSION of include/sei_hip.h this table was written against
 

@@ -11,10 +11,13 @@ unpinned), the trivial "Identity" and "InverseFilter", the bicubic "Upsample" ba
 (models/tv.py: proximal gradient on the sei_tv_prox kernel; it needs --tv_lambd, for which the reference has no default
 either) and "DeepImagePrior" (models/dip.py: deepinv's untrained ConvDecoder restated, fitted to each measurement by Adam on
 the fused sei_dip_* kernels; parity with deepinv unpinned, the float64 restatement in tests/test_dip_baseline_gpu.py is the
-pinned truth; --dip_iterations, with the reference's defaults for deblurring and sr). The other test-time baselines (PnP,
-BM3D, DiffPIR, DPS) need pretrained networks or a package that is not here; they raise a clear error instead of silently
-running something else. (The one pretrained network that IS rebuilt sits outside this factory: the AlexNet features of the
-LPIPS metric, metrics.LPIPS, five convolutions whose two small published weight files the user names to test.py.)
+pinned truth; --dip_iterations, with the reference's defaults for deblurring and sr) and "PlugAndPlay" (models/pnp.py:
+DPIR half-quadratic splitting around the DRUNet of models/drunet.py on the fused sei_drunet_* kernels; the user names the
+pretrained weights with --drunet_weights, nothing is fetched; parity with deepinv unpinned, tests/drunet_ref.py is the
+pinned truth). The other test-time baselines (BM3D, DiffPIR, DPS) need pretrained networks or a package that is not here;
+they raise a clear error instead of silently running something else. (A second pretrained network sits outside this
+factory: the AlexNet features of the LPIPS metric, metrics.LPIPS, five convolutions whose two small published weight files
+the user names to test.py.)
 """
 from os import environ
 
@@ -26,9 +29,11 @@ from physics._ops import SeparableResampleOp, apply_linear
 from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
 from .dip import DeepImagePrior
+from .drunet import DRUNet
+from .pnp import PnPModel
 from .tv import TV
 
-_OUT_OF_SCOPE = ("PlugAndPlay", "BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS")
+_OUT_OF_SCOPE = ("BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS")
 
 
 class Identity(Module):
@@ -110,6 +115,13 @@ class Model(Module):
             self.model = TV(physics=physics, **blueprint[TV.__name__])
         elif kind == "DeepImagePrior":                        # reference :109-114: sr_factor whatever the task
             self.model = DeepImagePrior(physics=physics, sr_factor=sr_factor, **blueprint[DeepImagePrior.__name__])
+        elif kind == "PlugAndPlay":                           # reference :115-122: early_stop=True, noise_level / 255
+            weights = blueprint[PnPModel.__name__]["drunet_weights"]
+            if weights is None:
+                raise NotImplementedError("model kind 'PlugAndPlay' runs a pretrained DRUNet and nothing is fetched: name "
+                                          "its state dict (KAIR's drunet_color.pth) with --drunet_weights")
+            self.model = PnPModel(physics=physics, noise_level_img=noise_level / 255, early_stop=True,
+                                  denoiser=DRUNet.from_file(weights, device))
         elif kind in _OUT_OF_SCOPE:
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
                                       "hot path this build implements")
@@ -179,6 +191,7 @@ def get_model(args, physics, device):
         # (train.py's parser has neither flag; the reference passes a missing --tv_lambd on as None and dies in deepinv,
         # TV raises NotImplementedError naming the flag)
         DeepImagePrior.__name__: {"iterations": _dip_iterations(args) if args.model_kind == "DeepImagePrior" else None},
+        PnPModel.__name__: {"drunet_weights": getattr(args, "drunet_weights", None)},
         TV.__name__: {"lambd": getattr(args, "tv_lambd", None), "max_iter": getattr(args, "tv_max_iter", None) or 300},
     }
     return Model(blueprint=blueprint, physics=physics, device=device,

@@ -13,11 +13,14 @@ kinds, `--dataset div2k | single_image | synthetic` or a directory of PNG measur
 backbone), `--r2r`, and the classical baseline `--model_kind TV --tv_lambd L [--tv_max_iter N]` (models/tv.py: proximal
 gradient on sei_tv_prox; without --tv_lambd it raises, the reference has no default either) and `--model_kind DeepImagePrior
 [--dip_iterations N]` (models/dip.py: an untrained decoder fitted to every measurement by Adam on the sei_dip_* kernels; its
-forward needs no autograd, so the reference's `dip` switch around no_grad has nothing to do here). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
+forward needs no autograd, so the reference's `dip` switch around no_grad has nothing to do here) and `--model_kind
+PlugAndPlay --drunet_weights FILE` (models/pnp.py: DPIR half-quadratic splitting, eight calls of the DRUNet of models/drunet.py
+on the sei_drunet_* kernels per image; FILE is the state dict of KAIR's drunet_color.pth, never fetched: without the flag it
+raises and names it). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
 `SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. `--lpips_backbone FILE --lpips_linear FILE`
 (build-side addition; both or neither) name a torchvision AlexNet state dict and the LPIPS v0.1 `alex` linear layers: the
 `LPIPS:`, `LPIPS std:` and `LIPS:` fields then carry metrics.lpips_fn's values (the sei_lpips_* kernels); without them they
-print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: PnP / BM3D / DiffPIR / DPS baselines (pretrained
+print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: BM3D / DiffPIR / DPS baselines (pretrained
 networks or the bm3d package).
 """
 import os
@@ -61,6 +64,7 @@ def build_parser():
     flag("--ssim", action="store_true")                                                  # build-side addition
     flag("--lpips_backbone", type=str, default=None, metavar="FILE")                     # build-side addition
     flag("--lpips_linear", type=str, default=None, metavar="FILE")                       # build-side addition
+    flag("--drunet_weights", type=str, default=None, metavar="FILE")                     # build-side addition
     return parser
 
 
