@@ -86,124 +86,123 @@ class GraphedLossStep:
         torch.cuda.set_rng_state(state, device)        # sizing the buffers must not advance the generator
 
         self.store_weight_grads = False
-
         # the root gradient (autograd would fill a fresh one per step); allocated OUTSIDE the graph's pool, so it must live
         # as long as the graph whose kernels read it
-        unit = self._unit_grad = torch.ones((), dtype=torch.float32, device=device)
-
-        def fwd_bwd():
-            self.backbone.zero_grad_flat(store_weight_grads=self.store_weight_grads)
-            value = self.inner(x=self.static_x, y=self.static_y, model=self.model, draws=self.static_draws)
-            if value.dim() == 0 and value.dtype == torch.float32:
-                value.backward(unit)
-            else:
-                value.backward()
-            return value.detach()
-
+        self._unit_grad = torch.ones((), dtype=torch.float32, device=device)
         from models import _ops
-        _ops.weight_grad_views(reset=True, owner=backbone)           # record this model's weight-gradient views only
-        _ops.reset_splitk_counters(device)
-        # warm-up AND capture on this one stream: the split-K workspace of the GEMMs belongs to a (device, stream), and a
-        # stream that first meets it while capturing gets none (models/_gemm.py splitk_workspace)
-        side = self._capture_stream = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            self._splitk_ws = _ops.own_splitk_workspace(device)      # this graph's own, alive as long as the graph is
-            for _ in range(warmup):                  # settle caches / allocator outside capture
-                fwd_bwd()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
+        self._ops = _ops
+        side = self._warm_up(warmup, device)
         # The captured step rebuilds the TRANSPOSED bf16 weight shadows from the plain bf16 copy, which
         # the fused Adam refreshes every step; make that copy current now, and re-check before each replay.
-        self._ops = _ops
-        _ops.refresh_plain_shadow(self.backbone)
+        _ops.refresh_plain_shadow(backbone)
         # The warm-up steps showed which gradients are written by the merged weight-gradient GEMMs; the
         # captured step stores those instead of accumulating and zeroes only the rest of the bucket.
-        self.store_weight_grads = store_weight_grads and \
-            self.backbone.plan_weight_grad_store(store_min_numel) is not None
+        self.store_weight_grads = store_weight_grads and backbone.plan_weight_grad_store(store_min_numel) is not None
         # Early release of the largest gradients: an EXTERNAL event recorded inside the captured backward right
         # after the two largest adjacent weight gradients (the bottleneck block: 83 % of the bucket at defaults)
         # have been written; `early_grads` = (event, start, stop) in bucket elements, or None.
-        self.early_grads = None
-        if self.store_weight_grads and early_release:
-            self.early_grads = self._plan_early_release(_ops)
-        self.fused_views, self.fused_table = [], None
-        if fuse_optimizer and self.store_weight_grads and hasattr(optimizer, "fuse_weight_updates") \
-                and _ops.get_compute_dtype(backbone) == "bf16" and getattr(optimizer, "reducer", None) is None:
-            grads = self.backbone.flat_grads
-            base, esz = grads.data_ptr(), grads.element_size()
-            for prm in self.backbone.parameters():
-                g = prm._sei_grad_view
-                off = (g.data_ptr() - base) // esz
-                if prm.dim() == 4 and prm.shape[2:] == (1, 1) and prm.numel() >= fuse_min_numel and off % 4 == 0 \
-                        and prm.shape[1] % 8 == 0 and g.data_ptr() in _ops.merged_weight_grads(backbone):
-                    self.fused_views.append(g.view(prm.shape[0], prm.shape[1]))
-            if self.fused_views:
-                self.fused_table = optimizer.fuse_weight_updates(self.fused_views)
-                _ops.set_fused_adam(*self.fused_table, owner=backbone)
-        # Several GPUs with a bf16-compressed exchange: the same weights' gradients go to the exchange buffer as bf16
-        # (no float32 copy, no cast pass); the reducer is told which slices not to cast after a replayed step.
-        self.direct_views = []
-        reducer = getattr(optimizer, "reducer", None)
-        if direct_bf16_grads and self.store_weight_grads and reducer is not None and reducer.comm is not reducer.flat \
-                and reducer.comm.dtype == torch.bfloat16 and _ops.get_compute_dtype(backbone) == "bf16":
-            grads = self.backbone.flat_grads
-            table, ranges = {}, []
-            for prm in self.backbone.parameters():
-                g = prm._sei_grad_view
-                off = (g.data_ptr() - grads.data_ptr()) // grads.element_size()
-                if prm.dim() == 4 and prm.shape[2:] == (1, 1) and prm.numel() >= fuse_min_numel and off % 4 == 0 \
-                        and prm.shape[1] % 8 == 0 and g.data_ptr() in _ops.merged_weight_grads(backbone):
-                    view = g.view(prm.shape[0], prm.shape[1])
-                    table[view.data_ptr()] = reducer.comm[off:off + prm.numel()].view(prm.shape[0], prm.shape[1])
-                    ranges.append((off, off + prm.numel()))
-                    self.direct_views.append(view)
-            if table:
-                reducer.set_direct_ranges(ranges)
-                _ops.set_direct_bf16_grads(table, owner=backbone)
-        self.graph = torch.cuda.CUDAGraph(keep_graph=True) if count_nodes else torch.cuda.CUDAGraph()
-        self.node_counts = None
+        self.early_grads = self._plan_early_release() if self.store_weight_grads and early_release else None
+        self._plan_sinks(fuse_optimizer, direct_bf16_grads, fuse_min_numel)
         try:
-            with torch.cuda.graph(self.graph, stream=side):
-                self.static_loss = fwd_bwd()
-            if self.direct_views and _ops.direct_bf16_launches(backbone) != {v.data_ptr() for v in self.direct_views}:
-                raise RuntimeError("bf16 gradients into the exchange buffer: not every registered weight was written "
-                                   "by the captured step")
-            if self.fused_views and _ops.fused_adam_launches(backbone) != {v.data_ptr() for v in self.fused_views}:
-                raise RuntimeError("fused optimizer step: not every registered weight was updated by the captured step")
-            if count_nodes:
-                import _native
-                self.node_counts = _native.graph_kernel_nodes(self.graph)
-                self.graph.instantiate()
+            self._capture(side, count_nodes)
         except Exception:
             if self.fused_views:
                 optimizer.unfuse_weight_updates()
             if self.direct_views:
-                reducer.set_direct_ranges([])
+                optimizer.reducer.set_direct_ranges([])
             raise
         finally:
             _ops.release_splitk_workspace(device, side, self._splitk_ws)
             _ops.set_weight_grad_milestone(None, None, owner=backbone)
             _ops.set_fused_adam(None, None, owner=backbone)
             _ops.set_direct_bf16_grads(None, owner=backbone)
-        self.backbone.zero_grad_flat()
+        backbone.zero_grad_flat()
 
-    def _plan_early_release(self, _ops):
+    def _fwd_bwd(self):
+        self.backbone.zero_grad_flat(store_weight_grads=self.store_weight_grads)
+        value = self.inner(x=self.static_x, y=self.static_y, model=self.model, draws=self.static_draws)
+        value.backward(self._unit_grad if value.dim() == 0 and value.dtype == torch.float32 else None)
+        return value.detach()
+
+    def _warm_up(self, steps, device):
+        """Eager steps that settle caches / the allocator and show the scheduler this model's weight gradients. Warm-up
+        AND capture run on the one stream returned: the split-K workspace of the GEMMs belongs to a (device, stream), and a
+        stream that first meets it while capturing gets none (models/_gemm.py splitk_workspace)."""
+        _ops = self._ops
+        _ops.weight_grad_views(reset=True, owner=self.backbone)      # record this model's weight-gradient views only
+        _ops.reset_splitk_counters(device)
+        side = self._capture_stream = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            self._splitk_ws = _ops.own_splitk_workspace(device)      # this graph's own, alive as long as the graph is
+            for _ in range(steps):
+                self._fwd_bwd()
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize(device)
+        return side
+
+    def _sink_candidates(self, min_numel):
+        """(param, 2-D gradient view, bucket offset) of every 1x1 weight whose gradient may go to a GEMM epilogue instead of
+        the bucket: large enough, aligned quads, and written by one merged launch in the warm-up steps."""
+        merged = self._ops.merged_weight_grads(self.backbone)
+        for prm in self.backbone.parameters():
+            g, off = prm._sei_grad_view, prm._sei_bucket_offset
+            if prm.dim() == 4 and prm.shape[2:] == (1, 1) and prm.numel() >= min_numel and off % 4 == 0 \
+                    and prm.shape[1] % 8 == 0 and g.data_ptr() in merged:
+                yield prm, g.view(prm.shape[0], prm.shape[1]), off
+
+    def _plan_sinks(self, fuse_optimizer, direct_bf16_grads, min_numel):
+        """One GPU: the optimizer step of the candidates inside their GEMM (`fused_views`, `fused_table`). Several GPUs with
+        a bf16-compressed exchange: their gradients go to the exchange buffer as bf16 (`direct_views`: no float32 copy, no
+        cast pass; the reducer is told which slices not to cast after a replayed step)."""
+        _ops, backbone, optimizer = self._ops, self.backbone, self.optimizer
+        reducer = getattr(optimizer, "reducer", None)
+        bf16 = self.store_weight_grads and _ops.get_compute_dtype(backbone) == "bf16"
+        self.fused_views, self.fused_table, self.direct_views = [], None, []
+        if fuse_optimizer and bf16 and hasattr(optimizer, "fuse_weight_updates") and reducer is None:
+            self.fused_views = [view for _, view, _ in self._sink_candidates(min_numel)]
+            if self.fused_views:
+                self.fused_table = optimizer.fuse_weight_updates(self.fused_views)
+                _ops.set_fused_adam(*self.fused_table, owner=backbone)
+        if direct_bf16_grads and bf16 and reducer is not None and reducer.comm is not reducer.flat \
+                and reducer.comm.dtype == torch.bfloat16:
+            found = list(self._sink_candidates(min_numel))
+            self.direct_views = [view for _, view, _ in found]
+            if found:
+                reducer.set_direct_ranges([(off, off + prm.numel()) for prm, _, off in found])
+                _ops.set_direct_bf16_grads({view.data_ptr(): reducer.comm[off:off + prm.numel()].view(view.shape)
+                                            for prm, view, off in found}, owner=backbone)
+
+    def _capture(self, side, count_nodes):
+        self.graph = torch.cuda.CUDAGraph(keep_graph=True) if count_nodes else torch.cuda.CUDAGraph()
+        self.node_counts = None
+        with torch.cuda.graph(self.graph, stream=side):
+            self.static_loss = self._fwd_bwd()
+        self._check_sink_launches(self.direct_views, self._ops.direct_bf16_launches, "bf16 gradients into the exchange buffer")
+        self._check_sink_launches(self.fused_views, self._ops.fused_adam_launches, "fused optimizer step")
+        if count_nodes:
+            import _native
+            self.node_counts = _native.graph_kernel_nodes(self.graph)
+            self.graph.instantiate()
+
+    def _check_sink_launches(self, views, launches, what):
+        if views and launches(self.backbone) != {v.data_ptr() for v in views}:
+            raise RuntimeError(f"{what}: not every registered weight was served by the captured step")
+
+    def _plan_early_release(self):
         base, esz = self.backbone.flat_grads.data_ptr(), self.backbone.flat_grads.element_size()
         total = self.backbone.flat_grads.numel()
-        views = sorted(((n, ptr) for ptr, n in _ops.weight_grad_views(owner=self.backbone).items()
+        views = sorted(((n, ptr) for ptr, n in self._ops.weight_grad_views(owner=self.backbone).items()
                         if base <= ptr < base + total * esz), reverse=True)
         if len(views) < 2:
             return None
-        (n0, p0), (n1, p1) = views[0], views[1]
-        lo, hi = min(p0, p1), max(p0, p1)
-        lo_n = n0 if lo == p0 else n1
-        start, stop = (lo - base) // esz, (hi - base) // esz + (n0 if hi == p0 else n1)
+        (lo, lo_n), (hi, hi_n) = sorted((ptr, n) for n, ptr in views[:2])
+        start, stop = (lo - base) // esz, (hi - base) // esz + hi_n
         if (hi - lo) // esz - lo_n >= 64 or (stop - start) < total // 4:       # not adjacent, or not worth it
             return None
         import _native
         event = _native.ExternalEvent()
-        _ops.set_weight_grad_milestone({p0, p1}, event, owner=self.backbone)
+        self._ops.set_weight_grad_milestone({lo, hi}, event, owner=self.backbone)
         return (event, int(start), int(stop))
 
     def _draw(self, given=None):

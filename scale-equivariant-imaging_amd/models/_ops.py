@@ -451,10 +451,9 @@ def cast16(x2d, colsum_into_=None, row_weight=None):
         # the column sums leave as per-row-block partial sums and join the pass's deferred folds (no atomics: the grid is
         # sized for bandwidth); outside a backward pass the atomics form below
         parts = N.lib().sei_cast_bf16_colsum_parts_count(R, C)
-        ms = _state_for(colsum_into_.data_ptr()).milestone
         # (a bias gradient between the two early-released weight gradients must be final when their event fires: such a
         # destination -- none in the U-Net, whose only bias there comes from a GEMM epilogue -- keeps the atomics)
-        early = ms is not None and min(ms[0]) <= colsum_into_.data_ptr() <= max(ms[0])
+        early = _state_for(colsum_into_.data_ptr()).in_early_release_range(colsum_into_.data_ptr())
         if parts > 0 and not early:
             work = torch.empty(parts * C, dtype=torch.float32, device=x2d.device)
             if defer_fold(colsum_into_, None, None, C, C, N.FOLD_SPLIT, work, 0, parts):

@@ -1,8 +1,11 @@
 """The weight-gradient scheduler: when, and as which launch, the weight gradient of a 1x1 convolution (or a linear
 layer of a Swin block) is issued. The layer functions (models/_ops.py, models/_swin_ops16.py) hand their operand pairs
 to `weight_grad16` / `weight_grad16_group` and their partial sums to `defer_fold`; everything else here is bookkeeping
-per backbone (`WeightGradState`), reached through thin module-level functions.
+per backbone (`WeightGradState`), reached through thin module-level functions: ONE record per gradient (`GradRecord`,
+whose docstring says which field lives how long), the pairs parked for the step's other model call, the queued streamed
+jobs and the deferred folds.
 """
+import collections
 import os
 import weakref
 
@@ -34,12 +37,19 @@ DWSTREAM = os.environ.get("SEI_NO_DWSTREAM") != "1"
 # deferred. SEI_NO_DEFERRED_FOLDS=1 restores the fold per launch.
 DEFERRED_FOLDS = os.environ.get("SEI_NO_DEFERRED_FOLDS") != "1"
 
-_NOT_MERGED = {
-    "adam": "fused optimizer step: a weight registered with set_fused_adam did not receive its "
-            "gradient as one merged storing GEMM (different loss / batch / call count than planned)",
-    "direct16": "bf16 gradients written into the exchange buffer: a registered weight did not receive its "
-                "gradient as one merged storing GEMM (different loss / batch / call count than planned)",
-}
+# The two epilogue sinks: the step's complete gradient is consumed by the epilogue of the GEMM that produces it. kind ->
+# (entry point, what a refusal calls it); the views registered with a kind are that entry point's arguments after the operands.
+SINK_ADAM, SINK_BF16 = "adam", "direct16"
+_SINKS = {SINK_ADAM: ("sei_gemm_bf16nt_dw2_adam", "fused optimizer step"),
+          SINK_BF16: ("sei_gemm_bf16nt_dw2_bf16out", "bf16 gradients written into the exchange buffer")}
+
+_Queued = collections.namedtuple("_Queued", "job operands grad flops")     # one entry of WeightGradState.dwjobs
+
+
+def _segments(pairs):
+    """(g1, x1, g2, x2, K1, K2) of the one or two (gy16, x16) row segments of a launch; a single one stands twice, K2 = 0."""
+    (g1, x1), (g2, x2) = pairs[0], pairs[-1]
+    return g1, x1, g2, x2, g1.shape[0], (g2.shape[0] if len(pairs) == 2 else 0)
 
 
 def colsum16_into(acc, x16):
@@ -50,18 +60,15 @@ def colsum16_into(acc, x16):
 
 def _dwstream_ok(grad2d, pairs):
     """The streamed launch serves this weight gradient (shapes, layouts, pixel counts)."""
-    if not DWSTREAM or not grad2d.is_cuda or grad2d.dim() != 2 or grad2d.dtype != torch.float32 or len(pairs) > 2:
+    if not DWSTREAM or not grad2d.is_cuda or grad2d.dim() != 2 or grad2d.dtype != torch.float32 or len(pairs) > 2 \
+            or grad2d.stride(1) != 1:
         return False
     Np, Kp = grad2d.shape
-    if grad2d.stride(1) != 1:
-        return False
     for gy, x in pairs:
         if not (gy.dtype == x.dtype == torch.bfloat16 and gy.is_contiguous() and x.is_contiguous()
                 and gy.dim() == 2 and x.dim() == 2 and gy.shape[1] == Np and x.shape[1] == Kp and gy.shape[0] == x.shape[0]):
             return False
-    K1 = pairs[0][0].shape[0]
-    K2 = pairs[1][0].shape[0] if len(pairs) == 2 else 0
-    return N.lib().sei_dwstream_bf16_eligible(Np, Kp, Np, Kp, K1, K2) != 0
+    return N.lib().sei_dwstream_bf16_eligible(Np, Kp, Np, Kp, *_segments(pairs)[4:]) != 0
 
 
 # ---------------------------------------------------------------------------------------------
@@ -78,95 +85,139 @@ def _dwstream_ok(grad2d, pairs):
 # of accumulating, and zero_grad skips those gradients -- valid because the captured step writes every one
 # of them exactly this way on every replay.
 # ---------------------------------------------------------------------------------------------
-class WeightGradState:
-    """The bookkeeping below, PER BACKBONE: model calls of the step, parked pairs, store / fused-Adam / direct-bf16
-    tables. Two models alive in one process (a frozen copy beside the fine-tuned one, two networks trained side by
-    side) each merge and store their own weight gradients. A backbone's state is found from the address of the
-    gradient a backward function writes (`register_gradient_range`: the flat gradient bucket, SwinPack's staging);
-    gradients outside every registered range (kernel-level tests) share the default state. Gradients are known by
-    their data_ptr (`key`)."""
+class GradRecord:
+    """What the scheduler knows about ONE gradient (`WeightGradState.records`, by data_ptr). Every field has one lifetime:
 
-    __slots__ = ("uses", "arrivals", "parked", "written", "store", "store_min", "merge", "flush_queued", "seen",
-                 "flops_per_row", "taps", "bias_of", "merged_ok", "milestone", "milestone_done", "adam", "adam_launched",
-                 "direct16", "direct16_launched", "dwjobs", "folds", "__weakref__")
+        lifetime      fields                                  set by                                 reset by
+        record        ident                                   creation (WeightGradState.record)      never
+        step          arrivals, written                       weight_grad16[_group], _launch         begin_step
+        launch        bias                                    weight_grad16(bias=)                   the next _issue (consumes it)
+        plan          numel, flops_per_row, taps, whole_step  weight_grad16[_group], _launch         weight_grad_views(reset=True)
+        registration  sink, sink_launched                     set_fused_adam, set_direct_bf16_grads  the same setter
+
+    An address met again with another shape or role -- taps or none: a freed model's tap-major gradient, now a 1x1 weight's
+    -- gets a new record: nothing noted for one gradient outlives it."""
+
+    __slots__ = ("ident", "arrivals", "written", "bias", "numel", "flops_per_row", "taps", "whole_step", "sink",
+                 "sink_launched")
+
+    def __init__(self, ident):
+        self.ident = ident                              # (shape, has taps)
+        self.arrivals, self.written = 0, False          # operand pairs handed in; launched into
+        self.bias = None                                # bias gradient whose column sums go with the weight's next launch
+        self.numel = self.flops_per_row = None          # of the view handed in; algorithmic FLOPs per reduction row to book
+        self.taps = None                                # tap row offsets of a (T, N', K') gradient
+        self.whole_step = False                         # its last launch was the step's complete gradient in one two-segment GEMM
+        self.sink, self.sink_launched = None, False     # (kind of _SINKS, views): that launch's epilogue consumes the gradient
+
+
+class WeightGradState:
+    """The bookkeeping below, PER BACKBONE: model calls of the step, one `GradRecord` per gradient, parked pairs. Two
+    models alive in one process (a frozen copy beside the fine-tuned one, two networks trained side by side) each merge
+    and store their own weight gradients. A backbone's state is found from the address of the gradient a backward
+    function writes (`register_gradient_range`: the flat gradient bucket, SwinPack's staging); gradients outside every
+    registered range (kernel-level tests) share the default state. Gradients are known by their data_ptr (`key`)."""
+
+    __slots__ = ("uses", "records", "parked", "store", "store_min", "merge", "flush_queued", "milestone", "milestone_done",
+                 "dwjobs", "folds", "__weakref__")
 
     def __init__(self):
         self.uses = 0                   # differentiated model calls of this step (note_forward)
-        self.arrivals = {}              # key -> operand pairs handed in this step
+        self.records = {}               # key -> GradRecord
         self.parked = {}                # key -> (gy16, x16, grad2d), or ("group", key) -> items: waiting for the other call
-        self.written = set()            # keys launched into this step
-        self.store = False              # store mode: a step's first launch into a gradient stores ...
-        self.store_min = 0              # ... when the gradient has at least this many elements
+        self.store, self.store_min = False, 0   # store mode: the first launch into a gradient of >= store_min elements stores
         self.merge = True               # park and merge across the step's model calls
         self.flush_queued = False       # the engine callback of the running backward pass is queued
-        self.seen = {}                  # key -> numel of every gradient view since the last weight_grad_views(reset=True)
-        self.flops_per_row = {}         # key -> algorithmic FLOPs per reduction row to book, or None
-        self.taps = {}                  # key -> tap row offsets of a (T, N', K') gradient
-        self.bias_of = {}               # key -> bias gradient whose column sums go with the weight's next launch
-        self.merged_ok = {}             # key -> its last launch was the step's complete gradient in one two-segment GEMM
-        self.milestone = None           # (frozenset of keys, event) or None (set_weight_grad_milestone)
-        self.milestone_done = False
-        self.adam = None                # ({key: (param, exp_avg, exp_avg_sq, shadow)}, hyper) or None (set_fused_adam)
-        self.adam_launched = set()
-        self.direct16 = None            # {key: bf16 view of the exchange buffer} or None (set_direct_bf16_grads)
-        self.direct16_launched = set()
-        self.dwjobs = []                # [(DwStreamJob, operands kept alive, flops)] queued for the streamed launch
+        self.milestone, self.milestone_done = None, False   # (frozenset of keys, event) or None (set_weight_grad_milestone)
+        self.dwjobs = []                # [_Queued] for the streamed launch; their operands live until it is issued
         self.folds = {}                 # destination pointer -> {"meta", "segs"}: deferred folds of the running pass
 
+    def record(self, key, shape, tapped=False):
+        """The record of the gradient of `shape` at `key`: a clean one unless the address is known in this shape and role."""
+        rec = self.records.get(key)
+        if rec is None or rec.ident != (tuple(shape), tapped):
+            rec = self.records[key] = GradRecord((tuple(shape), tapped))
+        return rec
+
+    def meet(self, grad, flops_per_row=None, taps=None):
+        """The record of `grad`, which a backward function hands in."""
+        rec = self.record(grad.data_ptr(), grad.shape, taps is not None)
+        rec.numel, rec.flops_per_row, rec.taps = grad.numel(), flops_per_row, taps
+        return rec
+
+    def set_sinks(self, kind, table):
+        """Register the epilogue sinks of `kind` -- table: key -> views -- in place of those registered before."""
+        for rec in self.records.values():
+            if rec.sink is not None and rec.sink[0] == kind:
+                rec.sink, rec.sink_launched = None, False
+        for key, views in (table or {}).items():
+            rec = self.record(key, views[0].shape)
+            rec.sink, rec.sink_launched = (kind, views), False
+
+    def sink_launches(self, kind):
+        return {k for k, r in self.records.items() if r.sink_launched and r.sink[0] == kind}
+
     # -- the launch decision --------------------------------------------------------------------------------
+    def arrive(self, pkey, n, entry, launch):
+        """The step's n-th model call brings `entry` for the gradient(s) parked under `pkey`: launched with the other call's
+        entry when that waits, parked while another call is to come (and a backward pass runs to flush it), else alone."""
+        partner = self.parked.pop(pkey, None)
+        if partner is not None:
+            launch([partner, entry])
+        elif self.merge and n < self.uses and self.queue_flush():
+            self.parked[pkey] = entry
+        else:
+            launch([entry])
+
     def may_store(self, grad2d):
-        """This launch into grad2d stores instead of accumulating: store mode, the step's first, a gradient large enough
-        to have been left out of zero_grad."""
-        return self.store and grad2d.data_ptr() not in self.written and grad2d.numel() >= self.store_min
+        """This launch stores instead of accumulating: store mode, the step's first, a gradient left out of zero_grad."""
+        return self.store and not self.records[grad2d.data_ptr()].written and grad2d.numel() >= self.store_min
 
     def whole_step(self, segments):
         """A launch over `segments` row segments carries the step's COMPLETE gradient: both model calls, merged."""
         return segments == 2 and segments == self.uses
 
-    def launch(self, grad2d, pairs):
-        key = grad2d.data_ptr()
-        store = self.may_store(grad2d)
-        self.written.add(key)
+    def _launch(self, keys, whole, issue):
+        """issue() launches into the gradients `keys`, with the whole step or not; the milestone is checked even if it raises."""
+        for rec in map(self.records.get, keys):
+            rec.written, rec.whole_step = True, whole
         try:
-            self._issue(grad2d, pairs, store)
+            issue()
         finally:
-            self.check_milestone(key)
+            for key in keys:
+                self.check_milestone(key)
+
+    def launch(self, grad2d, pairs):
+        store = self.may_store(grad2d)
+        whole = self.whole_step(len(pairs)) and sum(gy16.shape[0] for gy16, _ in pairs) % 8 == 0   # (rows the dw2 kernels take)
+        self._launch([grad2d.data_ptr()], whole, lambda: self._issue(grad2d, pairs, store))
 
     def _issue(self, grad2d, pairs, store):
-        key = grad2d.data_ptr()
+        rec = self.records[grad2d.data_ptr()]
         # (weight_grad16(..., bias=): the bias gradient = gy's column sums rides in the streamed launch where that serves
         # the weight, else it is summed here, one column-sum launch per pair.)
-        bias = self.bias_of.pop(key, None)
+        bias, rec.bias = rec.bias, None
         if bias is not None and (store or not _dwstream_ok(grad2d, pairs)):
             for gy16, _ in pairs:
                 colsum16_into(bias, gy16)
             bias = None
         Np, Kp = grad2d.shape[-2:]
-        (g1, x1), (g2, x2) = pairs if len(pairs) == 2 else (pairs[0], pairs[0])
-        K1, K2 = g1.shape[0], (g2.shape[0] if len(pairs) == 2 else 0)
-        complete = self.whole_step(len(pairs)) and (K1 + K2) % 8 == 0      # ... in rows the dw2 kernels take
-        self.merged_ok[key] = complete
-        table = "adam" if self.adam is not None and key in self.adam[0] else \
-            "direct16" if self.direct16 is not None and key in self.direct16 else None
-        if table is not None:
+        g1, x1, g2, x2, K1, K2 = _segments(pairs)
+        operands = (g1.data_ptr(), g2.data_ptr(), Np, x1.data_ptr(), x2.data_ptr(), Kp)
+        if rec.sink is not None:
             # the update (the bf16 gradient) replaces the stored gradient only when this launch IS the step's whole gradient
-            launched = self.adam_launched if table == "adam" else self.direct16_launched
-            if not (store and complete) or key in launched:
-                raise RuntimeError(_NOT_MERGED[table])
-            launched.add(key)
-            if table == "adam":
-                prm, m1, v1, sh = self.adam[0][key]
-                _gemm_call(2.0 * Np * Kp * (K1 + K2), "sei_gemm_bf16nt_dw2_adam", g1.data_ptr(), g2.data_ptr(), Np,
-                           x1.data_ptr(), x2.data_ptr(), Kp, prm.data_ptr(), m1.data_ptr(), v1.data_ptr(), N.ptr(sh),
-                           self.adam[1].data_ptr(), Np, Kp, K1, K2)
-            else:
-                _gemm_call(2.0 * Np * Kp * (K1 + K2), "sei_gemm_bf16nt_dw2_bf16out", g1.data_ptr(), g2.data_ptr(), Np,
-                           x1.data_ptr(), x2.data_ptr(), Kp, self.direct16[key].data_ptr(), Np, Kp, K1, K2)
+            kind, views = rec.sink
+            entry, what = _SINKS[kind]
+            if not (store and rec.whole_step) or rec.sink_launched:
+                raise RuntimeError(f"{what}: a registered weight did not receive its gradient as one merged storing GEMM "
+                                   "(different loss / batch / call count than planned)")
+            rec.sink_launched = True
+            _gemm_call(2.0 * Np * Kp * (K1 + K2), entry, *operands, *[N.ptr(v) for v in views], Np, Kp, K1, K2)
             return
-        taps = self.taps.get(key)
+        taps = rec.taps
         if taps is not None:                               # (T, N', K') gradient: every tap in one launch
             T = grad2d.shape[0]
-            per_row = self.flops_per_row.get(key) or 2.0 * T * Np * Kp
+            per_row = rec.flops_per_row or 2.0 * T * Np * Kp
             if (K1 + K2) % 8 != 0:
                 raise ValueError("weight_grad16 with taps: the reduction length must be a multiple of 8 rows")
             if TOKEN_STREAMING and not store and Np == 192 and Kp == 192 and T <= N.TOKGRAD_MAX_BLOCKS \
@@ -182,16 +233,15 @@ class WeightGradState:
                 arr = (N.TokGradBlock * T)(*blocks)
                 _gemm_call(per_row * (K1 + K2), "sei_tokgrad_bf16_blocks", arr, T, K1, K2)
                 return
-            _gemm_call(per_row * (K1 + K2), "sei_gemm_bf16nt_dw2_taps", g1.data_ptr(), g2.data_ptr(), Np, x1.data_ptr(),
-                       x2.data_ptr(), Kp, grad2d.data_ptr(), Np, Kp, K1, K2, 0 if store else 1, T, taps, Np * Kp)
+            _gemm_call(per_row * (K1 + K2), "sei_gemm_bf16nt_dw2_taps", *operands, grad2d.data_ptr(), Np, Kp, K1, K2,
+                       int(not store), T, taps, Np * Kp)
             return
-        per_row = self.flops_per_row.get(key) or 2.0 * Np * Kp
+        per_row = rec.flops_per_row or 2.0 * Np * Kp
         if not store and self.queue_dwstream(grad2d, pairs, per_row, bias):
             return
         assert bias is None
         if len(pairs) == 2 and (K1 + K2) % 8 == 0:
-            _gemm_call(per_row * (K1 + K2), "sei_gemm_bf16nt_dw2", g1.data_ptr(), g2.data_ptr(), Np,
-                       x1.data_ptr(), x2.data_ptr(), Kp, grad2d.data_ptr(), Np, Kp, K1, K2, 0 if store else 1)
+            _gemm_call(per_row * (K1 + K2), "sei_gemm_bf16nt_dw2", *operands, grad2d.data_ptr(), Np, Kp, K1, K2, int(not store))
             return
         for gy16, x16 in pairs:
             rows = gy16.shape[0]
@@ -207,15 +257,12 @@ class WeightGradState:
         row) per model call of the step, the layers in the same order -- as ONE token-streamed launch
         (sei_tokgrad_bf16_blocks: every 192 x 192 block of every gradient on its share of the CUs) when the shapes allow
         it and every gradient accumulates; one launch per layer otherwise."""
-        first = segs[0]
+        grads = [item[2] for item in segs[0]]
         rows = [seg[0][0].shape[0] for seg in segs]
         blocks, ok = [], TOKEN_STREAMING and len(segs) <= 2 and all(r % 64 == 0 for r in rows)
-        for i, (_, _, grad2d, _) in enumerate(first):
-            key = grad2d.data_ptr()
+        for i, grad2d in enumerate(grads):
             ok = ok and grad2d.dim() == 2 and grad2d.is_contiguous() and grad2d.dtype == torch.float32
-            ok = ok and not self.may_store(grad2d)
-            ok = ok and not (self.adam is not None and key in self.adam[0])
-            ok = ok and not (self.direct16 is not None and key in self.direct16) and key not in self.taps
+            ok = ok and not self.may_store(grad2d) and self.records[grad2d.data_ptr()].sink is None
             for s, seg in enumerate(segs):
                 gy, x = seg[i][0], seg[i][1]
                 ok = ok and gy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and gy.is_contiguous() and x.is_contiguous()
@@ -232,45 +279,41 @@ class WeightGradState:
                     blocks.append(N.TokGradBlock(a[0].data_ptr(), b[0].data_ptr(), a[1].data_ptr(), b[1].data_ptr(), Mo, Ni,
                                                  192 * gy, 192 * gx, grad2d.data_ptr() + 4 * (192 * gy * Ni + 192 * gx), Ni))
         if not ok or len(blocks) > 8:
-            for i, (_, _, grad2d, _) in enumerate(first):
+            for i, grad2d in enumerate(grads):
                 self.launch(grad2d, [(seg[i][0], seg[i][1]) for seg in segs])
             return
-        flops = 0.0
-        for _, _, grad2d, fpr in first:
-            key = grad2d.data_ptr()
-            self.written.add(key)
-            self.merged_ok[key] = self.whole_step(len(segs))
-            flops += (fpr or 2.0 * grad2d.shape[0] * grad2d.shape[1]) * sum(rows)
+        flops = sum((fpr or 2.0 * g.shape[0] * g.shape[1]) * sum(rows) for _, _, g, fpr in segs[0])
         arr = (N.TokGradBlock * len(blocks))(*blocks)
-        try:
-            _gemm_call(flops, "sei_tokgrad_bf16_blocks", arr, len(blocks), rows[0], rows[1] if len(rows) == 2 else 0)
-        finally:
-            for _, _, grad2d, _ in first:
-                self.check_milestone(grad2d.data_ptr())
+        self._launch([g.data_ptr() for g in grads], self.whole_step(len(segs)), lambda: _gemm_call(
+            flops, "sei_tokgrad_bf16_blocks", arr, len(blocks), rows[0], rows[1] if len(rows) == 2 else 0))
 
     def check_milestone(self, key):
         ms = self.milestone
-        if ms is not None and key in ms[0] and ms[0] <= self.written and not self.milestone_done:
-            # every gradient of the milestone has had its (single, merged) launch of this step
-            if all(self.arrivals.get(k, 0) >= max(self.uses, 1) for k in ms[0]):
-                # a milestone gradient that was only QUEUED for the streamed launch (flush at the end of the backward pass)
-                # must be on the stream before the event that releases it to the reducer
-                if any(job[1][4].data_ptr() in ms[0] for job in self.dwjobs):
-                    self.flush_dwstream()
-                ms[1].record()
-                self.milestone_done = True
+        if ms is None or key not in ms[0] or self.milestone_done:
+            return
+        # every gradient of the milestone has had its (single, merged) launch of this step
+        if all(r is not None and r.written and r.arrivals >= max(self.uses, 1) for r in map(self.records.get, ms[0])):
+            # a milestone gradient that was only QUEUED for the streamed launch (flush at the end of the backward pass)
+            # must be on the stream before the event that releases it to the reducer
+            if any(q.grad.data_ptr() in ms[0] for q in self.dwjobs):
+                self.flush_dwstream()
+            ms[1].record()
+            self.milestone_done = True
+
+    def in_early_release_range(self, ptr):
+        """`ptr` lies between the gradients of the milestone: whatever is written there must be final when its event fires."""
+        ms = self.milestone
+        return ms is not None and min(ms[0]) <= ptr <= max(ms[0])
 
     # -- streamed weight gradients (DWSTREAM above) ---------------------------------------------------------
     def queue_dwstream(self, grad2d, pairs, per_row, bias=None):
         if not _dwstream_ok(grad2d, pairs):
             return False
         Np, Kp = grad2d.shape
-        K1 = pairs[0][0].shape[0]
-        K2 = pairs[1][0].shape[0] if len(pairs) == 2 else 0
-        (g1, x1), (g2, x2) = pairs[0], pairs[-1]
+        g1, x1, g2, x2, K1, K2 = _segments(pairs)
         job = N.DwStreamJob(g1.data_ptr(), g2.data_ptr(), x1.data_ptr(), x2.data_ptr(), Np, Kp, Np, Kp, grad2d.data_ptr(),
                             grad2d.stride(0), 0, K1, K2, N.ptr(bias))
-        self.dwjobs.append((job, (g1, x1, g2, x2, grad2d, bias), per_row * (K1 + K2)))
+        self.dwjobs.append(_Queued(job, (g1, x1, g2, x2, bias), grad2d, per_row * (K1 + K2)))
         if len(self.dwjobs) == N.DWSTREAM_MAX_JOBS or not self.queue_flush():
             self.flush_dwstream()
         return True
@@ -279,8 +322,8 @@ class WeightGradState:
         jobs, self.dwjobs = self.dwjobs, []
         if not jobs:
             return
-        arr = (N.DwStreamJob * len(jobs))(*[j[0] for j in jobs])
-        _gemm_call(sum(j[2] for j in jobs), "sei_dwstream_bf16_jobs", arr, len(jobs))   # (the operands in `jobs` live until here)
+        arr = (N.DwStreamJob * len(jobs))(*[q.job for q in jobs])
+        _gemm_call(sum(q.flops for q in jobs), "sei_dwstream_bf16_jobs", arr, len(jobs))   # (`jobs` kept the operands alive)
 
     # -- deferred folds (DEFERRED_FOLDS above) --------------------------------------------------------------
     def defer_fold(self, a, b, c, ncol, split, kind, work, offset, groups):
@@ -332,8 +375,7 @@ class WeightGradState:
             if isinstance(entry, list):                    # a parked group (weight_grad16_group)
                 self.launch_group([entry])
             else:
-                gy16, x16, grad2d = entry
-                self.launch(grad2d, [(gy16, x16)])
+                self.launch(entry[2], [entry[:2]])
         self.flush_dwstream()
         self.flush_folds()
 
@@ -384,11 +426,10 @@ def begin_step(store=False, store_min=0, owner=None):
     if rec is not None:
         rec.reset()
     st.uses = 0
-    st.arrivals.clear()
-    st.written.clear()
+    for r in st.records.values():
+        r.arrivals, r.written = 0, False
     st.milestone_done = False
-    st.store = bool(store)
-    st.store_min = int(store_min)
+    st.store, st.store_min = bool(store), int(store_min)
 
 
 def set_weight_grad_merging(enabled, owner=None):
@@ -400,12 +441,10 @@ def set_weight_grad_merging(enabled, owner=None):
 def weight_grad_views(reset=False, owner=None):
     """{data_ptr: numel} of every gradient view written through weight_grad16 since the last reset."""
     st = state_of(owner)
-    seen = dict(st.seen)
+    seen = {k: r.numel for k, r in st.records.items() if r.numel is not None}
     if reset:
-        st.seen.clear()
-        st.taps.clear()
-        st.merged_ok.clear()
-        st.flops_per_row.clear()
+        for r in st.records.values():
+            r.numel, r.flops_per_row, r.taps, r.whole_step = None, None, None, False
     return seen
 
 
@@ -421,9 +460,7 @@ def set_fused_adam(table, hyper, owner=None):
     data_ptr of a gradient view to the (param, exp_avg, exp_avg_sq, bf16 shadow or None) views of the same shape,
     `hyper` is the device array of the step's six Adam scalars. The step's single, merged, storing launch into such a
     gradient applies the update instead of writing the gradient (sei_gemm_bf16nt_dw2_adam); None switches it off."""
-    st = state_of(owner)
-    st.adam = (dict(table), hyper) if table else None
-    st.adam_launched = set()
+    state_of(owner).set_sinks(SINK_ADAM, {k: tuple(v) + (hyper,) for k, v in table.items()} if table else None)
 
 
 def set_direct_bf16_grads(table, owner=None):
@@ -431,25 +468,23 @@ def set_direct_bf16_grads(table, owner=None):
     view to the bf16 view of the exchange buffer with the same shape. The step's single, merged, storing launch into
     such a gradient writes bf16 there (sei_gemm_bf16nt_dw2_bf16out) and nothing into the float32 bucket, which the
     reducer then does not cast for those ranges; None switches it off."""
-    st = state_of(owner)
-    st.direct16 = dict(table) if table else None
-    st.direct16_launched = set()
+    state_of(owner).set_sinks(SINK_BF16, {k: (v,) for k, v in table.items()} if table else None)
 
 
 def direct_bf16_launches(owner=None):
-    return set(state_of(owner).direct16_launched)
+    return state_of(owner).sink_launches(SINK_BF16)
 
 
 def fused_adam_launches(owner=None):
     """data_ptrs whose update was applied inside a GEMM since set_fused_adam."""
-    return set(state_of(owner).adam_launched)
+    return state_of(owner).sink_launches(SINK_ADAM)
 
 
 def merged_weight_grads(owner=None):
     """data_ptrs of the gradients whose last launch carried the step's COMPLETE gradient as one two-segment GEMM (the
     condition for applying the optimizer step, or writing bf16, in that launch: graphs.GraphedLossStep reads this after
     its warm-up steps -- a batch whose pixel counts do not add up to a multiple of 8 rows is served by other launches)."""
-    return {k for k, ok in state_of(owner).merged_ok.items() if ok}
+    return {k for k, r in state_of(owner).records.items() if r.whole_step}
 
 
 def flush_weight_grads(owner=None):
@@ -466,31 +501,19 @@ def weight_grad16(gy16, x16, grad2d, flops_per_row=None, tap_rows=None, bias=Non
     the un-shifted window of a grid with guard rows on both sides."""
     key = grad2d.data_ptr()
     st = _state_for(key)
-    st.seen[key] = grad2d.numel()
-    st.flops_per_row[key] = flops_per_row
+    rec = st.meet(grad2d, flops_per_row, tap_rows)
     if bias is not None:                   # (M,)-shaped float32 gradient: += gy's column sums, with the weight's launch
-        st.bias_of[key] = bias
-    if tap_rows is not None:
-        st.taps[key] = tap_rows
-    else:
-        st.taps.pop(key, None)              # the address may have belonged to a freed model's tap-major gradient
+        rec.bias = bias
     split = _gemm._JOINT_SPLIT
     if split is not None and tap_rows is None:
         # one backward pass for the step's two model calls (models/_joint.py): the operands hold both calls' rows -- the
         # two row segments that two backward functions would otherwise have brought one after the other
         M1 = gy16.shape[0] * split[0] // (split[0] + split[1])
-        st.arrivals[key] = st.arrivals.get(key, 0) + 2
+        rec.arrivals += 2
         st.launch(grad2d, [(gy16[:M1], x16[:M1]), (gy16[M1:], x16[M1:])])
         return
-    n = st.arrivals.get(key, 0) + 1
-    st.arrivals[key] = n
-    partner = st.parked.pop(key, None)
-    if partner is not None:
-        st.launch(grad2d, [partner[:2], (gy16, x16)])
-    elif st.merge and n < st.uses and st.queue_flush():
-        st.parked[key] = (gy16, x16, grad2d)
-    else:
-        st.launch(grad2d, [(gy16, x16)])
+    rec.arrivals += 1
+    st.arrive(key, rec.arrivals, (gy16, x16, grad2d), lambda entries: st.launch(grad2d, [e[:2] for e in entries]))
 
 
 def weight_grad16_group(items):
@@ -500,21 +523,9 @@ def weight_grad16_group(items):
     items = list(items)
     head = items[0][2].data_ptr()
     st = _state_for(head)
-    for gy16, x16, grad2d, fpr in items:
-        key = grad2d.data_ptr()
-        st.seen[key] = grad2d.numel()
-        st.flops_per_row[key] = fpr
-        st.taps.pop(key, None)
-        st.arrivals[key] = st.arrivals.get(key, 0) + 1
-    n = st.arrivals[head]
-    gkey = ("group", head)
-    partner = st.parked.pop(gkey, None)
-    if partner is not None:
-        st.launch_group([partner, items])
-    elif st.merge and n < st.uses and st.queue_flush():
-        st.parked[gkey] = items
-    else:
-        st.launch_group([items])
+    for _, _, grad2d, fpr in items:
+        st.meet(grad2d, fpr).arrivals += 1
+    st.arrive(("group", head), st.records[head].arrivals, items, st.launch_group)
 
 
 def defer_fold(a, b, c, ncol, split, kind, work, offset, groups):

@@ -240,53 +240,42 @@ class FlatAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         flat, grads = self.backbone.flat_params, self.backbone.flat_grads
         N.check_tensor(flat, "flat_params")
-        group = self.param_groups[0]
-        st = self.state[flat]
+        group, st = self.param_groups[0], self.state[flat]
         st["step"] += 1
-        whole = False
-        if self._fused_ranges and self._prepared_for != st["step"]:
-            # not a replayed step: fine after zero_grad() + an eager backward pass (a short last batch), which wrote every
-            # gradient the ordinary way; anything else would step the fused weights on gradients nobody computed
-            if not self._eager_grads:
-                st["step"] -= 1
-                raise RuntimeError("FlatAdam.step(): part of this step is applied inside the captured backward pass, "
-                                   "which was not replayed with prepare_step() for this step "
-                                   "(graphs.GraphedLossStep does both)")
-            whole = True
+        # not a replayed step: fine after zero_grad() + an eager backward pass (a short last batch), which wrote every
+        # gradient the ordinary way (the step then covers the WHOLE bucket); anything else would step the fused weights on
+        # gradients nobody computed
+        whole = bool(self._fused_ranges) and self._prepared_for != st["step"]
+        if whole and not self._eager_grads:
+            st["step"] -= 1
+            raise RuntimeError("FlatAdam.step(): part of this step is applied inside the captured backward pass, which was "
+                               "not replayed with prepare_step() for this step (graphs.GraphedLossStep does both)")
         self._eager_grads = False
         b1, b2 = group["betas"]
-        world = 1
+        world, exchanging = 1, False
         bounds = self._step_bounds(flat.numel(), whole)
-        grads_16 = False
-        exchanging = False
         if self.reducer is not None:
             from parallel import exchange_active, world_size
-            world = world_size()
-            exchanging = exchange_active()
+            world, exchanging = world_size(), exchange_active()
             bounds = self.reducer.bounds
             grads = self.reducer.comm                     # the (possibly bf16-compressed) reduced bucket
-            grads_16 = grads.dtype == torch.bfloat16
         from models import _ops
         shadow = getattr(self.backbone, "flat_shadow", None) if _ops.get_compute_dtype(self.backbone) == "bf16" else None
-        if self.reducer is not None and self.reducer.mode == "sharded" and exchanging:
-            def update(lo, hi, g, g16):
-                N.call("sei_adam_fused", flat[lo:hi].data_ptr(), g.data_ptr(), int(g16), st["exp_avg"][lo:hi].data_ptr(),
-                       st["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, float(group["lr"]), float(b1), float(b2),
-                       float(group["eps"]), float(group["weight_decay"]), int(st["step"]), 1.0 / world,
-                       None if shadow is None else shadow[lo:hi].data_ptr())
-            self._step_sharded(update, shadow)
-            _ops.weights_updated(self.backbone, plain_shadow_written=shadow is not None)
-            return
-        order = self.reducer.order if self.reducer is not None else range(len(bounds))
-        for k in order:                                   # chunks in the order their all-reduces complete
-            s, e = bounds[k]
-            if self.reducer is not None:
-                self.reducer.wait(k)
-            N.call("sei_adam_fused", flat[s:e].data_ptr(), grads[s:e].data_ptr(), int(grads_16),
-                   st["exp_avg"][s:e].data_ptr(),
-                   st["exp_avg_sq"][s:e].data_ptr(), e - s, float(group["lr"]), float(b1), float(b2),
+
+        def update(lo, hi, g, g16):
+            N.call("sei_adam_fused", flat[lo:hi].data_ptr(), g.data_ptr(), int(g16), st["exp_avg"][lo:hi].data_ptr(),
+                   st["exp_avg_sq"][lo:hi].data_ptr(), hi - lo, float(group["lr"]), float(b1), float(b2),
                    float(group["eps"]), float(group["weight_decay"]), int(st["step"]), 1.0 / world,
-                   None if shadow is None else shadow[s:e].data_ptr())
+                   None if shadow is None else shadow[lo:hi].data_ptr())
+
+        if self.reducer is not None and self.reducer.mode == "sharded" and exchanging:
+            self._step_sharded(update, shadow)
+        else:
+            for k in (self.reducer.order if self.reducer is not None else range(len(bounds))):
+                s, e = bounds[k]                          # chunks in the order their all-reduces complete
+                if self.reducer is not None:
+                    self.reducer.wait(k)
+                update(s, e, grads[s:e], grads.dtype == torch.bfloat16)
         # bf16 weight shadows must be rebuilt before the next forward (the plain copy just was, if asked)
         _ops.weights_updated(self.backbone, plain_shadow_written=shadow is not None)
 

@@ -670,6 +670,44 @@ def test_weight_gradient_reduction_major(ops, M, Np, Kp):
     assert relerr(acc, ref) < 5e-6
 
 
+def test_weight_gradient_address_reused_with_another_role(ops):
+    """What the scheduler remembers about a gradient belongs to (address, shape, taps or not): a (64, 64) gradient at the
+    address where a (9, 64, 64) tap-major one was written before -- a freed model's, say -- is an ordinary weight gradient
+    (no tap launch), and a bias gradient handed in with one launch is not summed again by the next."""
+    import ctypes
+    import _native
+    gen = torch.Generator().manual_seed(64)
+    M, C, Wp = 64, 64, 6
+    guard = Wp + 9                                              # as Conv3x3GemmFn16: tap shifts (<= Wp + 1) + rounding
+    offsets = [(ky - 1) * Wp + (kx - 1) for ky in range(3) for kx in range(3)]
+    gy = torch.randn((M, C), generator=gen).bfloat16()
+    xp = torch.randn((M + 2 * guard, C), generator=gen).bfloat16()
+    gyd, xpd = gy.cuda(), xp.cuda()
+    x16 = xpd[guard:guard + M]
+    ops.begin_step()
+    buf = torch.zeros((9, C, C), device="cuda")
+    ops.weight_grad16(gyd, x16, buf, tap_rows=(ctypes.c_int * 9)(*offsets))
+    taps = torch.stack([gy.double().T @ xp[guard + o:guard + o + M].double() for o in offsets])
+    assert relerr(buf, taps) < 5e-6
+    before = buf[0].double().cpu()
+    product = gy.double().T @ xp[guard:guard + M].double()
+    bias = torch.zeros(C, device="cuda")
+    _native.record_calls(True)
+    try:
+        ops.weight_grad16(gyd, x16, buf[0], bias=bias)
+    finally:
+        names = [n for n, _ in _native.record_calls(False)]
+    assert "sei_gemm_bf16nt_dw2_taps" not in names and "sei_tokgrad_bf16_blocks" not in names, names
+    assert buf[0].data_ptr() == buf.data_ptr()
+    assert relerr(buf[0], before + product) < 5e-6
+    assert relerr(bias, gy.double().sum(0)) < 5e-6
+    assert relerr(buf[1:], taps[1:]) < 5e-6                     # the other taps' memory was not written
+    kept = bias.clone()
+    ops.weight_grad16(gyd, x16, buf[0])
+    assert torch.equal(bias, kept)                              # a pending bias does not outlive its launch
+    assert relerr(buf[0], before + 2 * product) < 5e-6
+
+
 @pytest.mark.parametrize("M,N,K", [(2304, 512, 128), (576, 2048, 512), (288, 512, 2048), (72, 8192, 2048), (4608, 128, 512)])
 def test_split_bf16_gemm_against_float64(ops, M, N, K):
     """models/_ops.py gemm_x3 (--compute_dtype bf16x3): every orientation and epilogue the float32 layer functions use,

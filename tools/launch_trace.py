@@ -1,7 +1,7 @@
-"""The host layer's launch sequence as data: for a list of small U-Net configurations, two training steps are run under
-`_native.record_calls` and every entry-point call is written as [name, arguments], non-pointer arguments verbatim, each
-pointer as null or the ordinal of that address's first appearance in the configuration's trace (job tables are unfolded
-field by field). Two traces taken on the same machine from two versions of the host code must be equal call for call when a
+"""The host layer's launch sequence as data: for a list of small U-Net configurations and one small SwinIR, two training
+steps are run under `_native.record_calls` and every entry-point call is written as [name, arguments], non-pointer arguments
+verbatim, each pointer as null or the ordinal of that address's first appearance in the configuration's trace (job tables
+are unfolded field by field, tables of plain integers -- tap offsets -- value by value). Two traces taken on the same machine from two versions of the host code must be equal call for call when a
 change claims to leave the launches alone.
 
     python tools/launch_trace.py --out trace.json                     # record (exit 1 if a required entry point is missing)
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scale-equivariant-imaging_amd"))
 sys.path.insert(1, ROOT)
 
-# (name, compute dtype, loss, crop, graphed, fused Adam). The proposed loss calls the model twice (the joint backward). The
+# (name, compute dtype, loss, crop, graphed, fused Adam[, early release]). The proposed loss calls the model twice (the joint backward). The
 # two "ragged" configurations crop to 36 pixels: pixel counts that are no multiple of 128, so the fused MLP backward takes
 # its column-sum branch -- they alone launch sei_colsum_bf16, and they alone have no sei_dwstream_bf16_jobs.
 CONFIGS = [(f"{dtype}-{method}-eager", dtype, method, 48, False, False)
@@ -28,19 +28,24 @@ CONFIGS += [(f"{dtype}-proposed-graph", dtype, "proposed", 48, True, False) for 
 CONFIGS += [("bf16-proposed-graph-fused-adam", "bf16", "proposed", 48, True, True),
             ("bf16-supervised-graph", "bf16", "supervised", 48, True, False),
             ("bf16-supervised-ragged", "bf16", "supervised", 36, False, False),
-            ("bf16-proposed-ragged", "bf16", "proposed", 36, False, False)]
+            ("bf16-proposed-ragged", "bf16", "proposed", 36, False, False),
+            # every weight gradient stored, and the event after the two largest recorded inside the captured backward
+            ("bf16-proposed-graph-early-release", "bf16", "proposed", 48, True, False, True)]
+# the bf16 SwinIR step at the smallest size the token-streaming kernels take, on them and on the tiled GEMMs
+SWIN_CONFIGS = [("swinir-bf16-streaming", True), ("swinir-bf16-tiled", False)]
 
 # every one of these must occur somewhere in the whole set: a shrunken configuration must not hide a branch
 # (sei_colsum_bf16 stands for the column-sum branch of the fused MLP backward)
 REQUIRED = ["sei_mlp_fused_fwd", "sei_mlp_fused_bwd", "sei_gemm_bf16nt", "sei_gemm_bf16nt_ws", "sei_transpose_bf16_many",
             "sei_cast_bf16", "sei_cast_bf16_colsum_parts", "sei_cast_transpose_bf16", "sei_split_bf16x2", "sei_split_bf16x3",
             "sei_dwstream_bf16_jobs", "sei_fold_many", "sei_ln_bwd_res", "sei_dwconv7_ln_fwd", "sei_dwconv7_bwd_weight_ex",
-            "sei_sepmap2_packed", "sei_conv3x3_bwd_weight_parts", "sei_colsum_bf16"]
+            "sei_sepmap2_packed", "sei_conv3x3_bwd_weight_parts", "sei_colsum_bf16", "sei_tokgrad_bf16_blocks",
+            "sei_gemm_bf16nt_dw2_taps", "sei_gemm_bf16nt_dw2", "sei_gemm_bf16nt_dw2_adam"]
 REQUIRED_ANY = [("sei_sepmap2_bf16", "sei_sepmap2_small", "sei_sepmap2_big")]
 WS_COLSUM_ARG = 16           # sei_gemm_bf16nt_ws: the column-sum destination
 
 
-def run_config(dtype, method, crop, graphed, fused_adam, batch=2):
+def run_config(dtype, method, crop, graphed, fused_adam, early_release=False, batch=2):
     """Two steps of one configuration -> the raw call log (GraphedLossStep: its warm-up and capture included)."""
     import torch
     import _native
@@ -67,9 +72,12 @@ def run_config(dtype, method, crop, graphed, fused_adam, batch=2):
     try:
         if graphed:
             step = GraphedLossStep(loss_fn, model, optimizer, (batch, 3, crop, crop), fuse_optimizer=fused_adam,
-                                   fuse_min_numel=1 << 18)
+                                   fuse_min_numel=1 << 18, early_release=early_release,
+                                   **({"store_min_numel": 0} if early_release else {}))
             if fused_adam and not step.fused_views:
                 raise RuntimeError("no weight took the fused Adam epilogue")
+            if early_release and step.early_grads is None:
+                raise RuntimeError("no early-release range was planned")
         for _ in range(2):
             if graphed:
                 step(x, y)
@@ -80,6 +88,43 @@ def run_config(dtype, method, crop, graphed, fused_adam, batch=2):
         torch.cuda.synchronize()
     finally:
         log = _native.record_calls(False)
+    return log
+
+
+def run_swin(streaming):
+    """Two bf16 steps of a small SwinIR (2 x 32 x 32: 2048 tokens, stochastic depth on) -> the raw call log."""
+    import torch
+    import _native
+    from models import _ops, _wgrad
+    from models.swinir import SwinIR
+    from optim import FlatAdam
+    from oracle import swinir_path
+    depths = (3, 2)
+    prev = _ops.set_compute_dtype("bf16")
+    _wgrad.TOKEN_STREAMING = streaming
+    try:
+        torch.manual_seed(11)
+        model = SwinIR(upscale=2, upsampler="pixelshuffle", depths=depths, num_heads=(6, 6)).cuda()
+        model.train()
+        optimizer = FlatAdam(model, lr=1e-4)
+        gen = torch.Generator().manual_seed(4)
+        x = torch.rand((2, 3, 32, 32), generator=gen).cuda()
+        go = torch.randn((2, 3, 64, 64), generator=gen).cuda()
+        masks = [None if m is None else tuple(v.cuda() for v in m)
+                 for m in swinir_path.draw_drop_masks(2, depths=depths, rate=0.4, generator=gen)]
+        torch.cuda.synchronize()
+        _native.record_calls(True)
+        try:
+            for _ in range(2):
+                optimizer.zero_grad()
+                model(x, drop_masks=masks).backward(go)
+                optimizer.step()
+            torch.cuda.synchronize()
+        finally:
+            log = _native.record_calls(False)
+    finally:
+        _wgrad.TOKEN_STREAMING = True
+        _ops.set_compute_dtype(prev)
     return log
 
 
@@ -105,8 +150,10 @@ def portable(log):
         for k, (a, ctype) in enumerate(zip(args, _native.SIGNATURES[name])):
             if ctype is not ctypes.c_void_p:
                 row.append(a)
-            elif isinstance(a, ctypes.Array):                  # a job table: one dict per job
+            elif isinstance(a, ctypes.Array) and issubclass(a._type_, ctypes.Structure):    # a job table: one dict per job
                 row.append([{f: field(getattr(job, f), t) for f, t in job._fields_} for job in a])
+            elif isinstance(a, ctypes.Array):                  # a table of integers (the tap offsets of a 3x3 convolution)
+                row.append(list(a))
             elif name == "sei_zero_ranges" and k == 1:         # (offset, count) pairs behind a host pointer
                 row.append(list((ctypes.c_ulonglong * (2 * args[2])).from_address(a.value)))
             else:
@@ -162,13 +209,13 @@ def main():
     if o.compare:
         return compare(*o.compare)
     traces = {}
-    for name, *cfg in CONFIGS:
+    for name, run, *cfg in [(c[0], run_config, *c[1:]) for c in CONFIGS] + [(c[0], run_swin, *c[1:]) for c in SWIN_CONFIGS]:
         if o.only and name not in o.only.split(","):
             continue
         gc.collect()
         gc.disable()            # (a cycle collection at another moment would free, and re-use, other addresses)
         try:
-            traces[name] = {"calls": portable(run_config(*cfg))}
+            traces[name] = {"calls": portable(run(*cfg))}
         except Exception as exc:                                # keep the other configurations' traces
             traces[name] = {"error": f"{type(exc).__name__}: {exc}"}
         finally:
