@@ -1007,6 +1007,51 @@ int sei_drunet_head(const float *x, float sigma, const uint16_t *Wt, int Cout, i
                     uint16_t *Y16, void *work, void *stream);
 int sei_drunet_tail(const uint16_t *X, const uint16_t *Wt, int Cin, int B, int H, int W, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The DiffPIR baseline around that denoiser (models/diffpir.py, models/_cg.py; deepinv v0.2.0's sampling.DiffPIR and
+ * optim.utils.conjugate_gradient restated): the data step's conjugate gradients with every scalar on the device, and the
+ * sampling step. float32 streaming kernels over flat tensors of n >= 1 elements (16-byte lanes, a scalar tail); tensor
+ * pointers 16-byte aligned. Each reduction leaves one partial per workgroup in `part` (sei_cg_partials(n) floats: the
+ * launch shape depends on n only) and a one-workgroup fold in the library's fold order writes the scalar into the state:
+ * no atomics, the same bits on every run. -ffp-contract=off: the expressions below are the float32 operations made.
+ *
+ * The solve is (A^T A + inv_gamma I) u = A^T y + inv_gamma u0 from u = 0, with deepinv's recurrences:
+ *   sei_cg_init       b = Aty + u0 * inv_gamma;  x = 0;  r = p = b;  state.rs = r . r;  done = iterations = 0.
+ *                     prologue = 1: u0 is first replaced by clamp(2 u0 - 1, -1, 1) / 2 + 0.5 (DiffPIR hands the denoiser's
+ *                     output over); 0: taken as it is.
+ *   [the caller's own kernels: AtAp = A^T A p]
+ *   sei_cg_apply      Ap = AtAp + p * inv_gamma;  state.pAp = p . Ap.
+ *   sei_cg_update     alpha = rs / pAp;  x += alpha p;  r -= alpha Ap;  state.rs_new = r . r;  iterations += 1;
+ *                     done = 1 when sqrt(rs_new) < tol (tol = 0: never); otherwise state.beta = rs_new / rs and then
+ *                     rs = rs_new (the fold behind the reduction is the one writer of the state and holds both values;
+ *                     the many workgroups of sei_cg_direction could not overwrite an rs they still read).
+ *   sei_cg_direction  p = r + p * beta, beta = rs_new / rs as sei_cg_update left it. Writes no state.
+ * Once done is set, _apply, _update and _direction return without writing anything: x is what deepinv's `break` leaves,
+ * updated by the stopping iteration, with p not advanced, however many further iterations the host has enqueued. The
+ * host reads done and iterations when it chooses to (models/_cg.py: every few iterations); nothing else of the solve
+ * leaves the device. */
+typedef struct SeiCgState {
+    float rs, pAp, rs_new;
+    int done, iterations;
+    float beta;           /* rs_new / rs of the last sei_cg_update, for sei_cg_direction */
+    int reserved[2];
+} SeiCgState;
+size_t sei_cg_partials(size_t n);
+int sei_cg_init(const float *u0, const float *Aty, float inv_gamma, int prologue, float *x, float *r, float *p, float *part,
+                SeiCgState *state, size_t n, void *stream);
+int sei_cg_apply(const float *p, const float *AtAp, float inv_gamma, float *Ap, float *part, SeiCgState *state, size_t n,
+                 void *stream);
+int sei_cg_update(float *x, float *r, const float *p, const float *Ap, float tol, float *part, SeiCgState *state, size_t n,
+                  void *stream);
+int sei_cg_direction(float *p, const float *r, const SeiCgState *state, size_t n, void *stream);
+/* One DiffPIR sampling step in one pass, from the prox result u (in [0, 1] scale) and the current iterate x:
+ *   x0 = 2 u - 1;  eps = (x - sa_t x0) / s1m_t;  x = sa_n x0 + s1m_n (sqrt(1 - zeta) eps + sqrt(zeta) nz)   (in place)
+ *   xin = x / (2 sqrt(at_n)) + 0.5                                                        (the next denoiser input)
+ * sa_* / s1m_* are sqrt(alphas_cumprod) / sqrt(1 - alphas_cumprod) at the current (t) and next (n) timestep, at_n the
+ * next alphas_cumprod; the three square roots are taken once on the host. u, nz, xin must not overlap x. */
+int sei_diffpir_sample(const float *u, float *x, const float *nz, float *xin, float sa_t, float s1m_t, float sa_n,
+                       float s1m_n, float zeta, float at_n, size_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,11 @@ SIGNATURES = {
     "sei_drunet_up": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "sei_drunet_head": [_P, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "sei_drunet_tail": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "sei_cg_init": [_P, _P, _F, _I, _P, _P, _P, _P, _P, _Z, _P],
+    "sei_cg_apply": [_P, _P, _F, _P, _P, _P, _Z, _P],
+    "sei_cg_update": [_P, _P, _P, _P, _F, _P, _P, _Z, _P],
+    "sei_cg_direction": [_P, _P, _P, _Z, _P],
+    "sei_diffpir_sample": [_P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _Z, _P],
 }
 
 _lib = None
@@ -189,6 +194,9 @@ class TransposeJob(_c.Structure):
 
 TRANSPOSE_MAX_JOBS = 16
 
+# SeiCgState of include/sei_hip.h as eight 4-byte words: rs, pAp, rs_new (float32), done, iterations (int32), beta (float32), 2 spare
+CG_STATE_WORDS, CG_DONE, CG_ITERATIONS = 8, 3, 4
+
 
 # size queries: return size_t, take no stream
 SIZE_QUERIES = {
@@ -224,6 +232,7 @@ SIZE_QUERIES = {
     "sei_cast_bf16_colsum_parts_count": [_I, _I],
     "sei_sgd_partials": [_Z, _Z, _I],
     "sei_drunet_work_bytes": [_I, _I, _I],
+    "sei_cg_partials": [_Z],
 }
 ABI_VERSION = 12      # SEI_ABI_VERSION of include/sei_hip.h this table was written against
 

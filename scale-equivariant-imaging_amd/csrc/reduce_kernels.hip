@@ -3,6 +3,7 @@
 //   sei_colsum_f32 / _weighted_f32 : bias gradients of the 1x1 convolutions (float atomics after an in-block LDS reduction)
 //   sei_fold_many / sei_fold_now   : the second stage of the depthwise, LayerNorm, cast and conv3x3 reductions -- the fold
 //                                    of per-workgroup partial sums, deferred (a job table) or at once (one job)
+//   sei_fold_cg                    : the same fold for one scalar of a conjugate-gradient solve (diffpir_kernels.hip)
 #include "sei_common.h"
 
 namespace {
@@ -300,6 +301,47 @@ int fold_job_check(const SeiFoldJob &J) {
     return 0;
 }
 }  // namespace
+
+namespace {
+// One scalar of a conjugate-gradient solve: part[groups] -> rs, pAp or rs_new of the state, in THE order (fold_entries
+// with one live entry, from 0.f), then the bookkeeping that hangs on that scalar. One workgroup, ordered behind the
+// reducing launch and ahead of the next reader: the only place the state's scalars are written. (A workgroup of
+// FOLD_SLICES x FOLD_ONE_E threads, as fold_one_kernel, so that the order is fold_entries' own; one column of it loads.)
+__global__ __launch_bounds__(FOLD_SLICES * FOLD_ONE_E) void fold_cg_kernel(SeiFoldJob J, SeiCgState *st, int target,
+                                                                            float tol) {
+    __shared__ float red[FOLD_SLICES * FOLD_ONE_E];
+    if (target != SEI_CG_FOLD_RS && st->done) return;            // a finished solve: its kernels left no partials
+    float *dst = J.a;                                            // &st->rs, &st->pAp or &st->rs_new
+    // fold_entries adds to what the destination holds: zero it first. The barriers make this independent of which thread
+    // of fold_entries reads and writes the destination.
+    if (threadIdx.x == 0) *dst = 0.f;
+    __syncthreads();
+    fold_entries<FOLD_ONE_E>(J, 0, red);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (target == SEI_CG_FOLD_RS) {                              // sei_cg_init: a new solve
+        st->done = 0;
+        st->iterations = 0;
+    } else if (target == SEI_CG_FOLD_RS_NEW) {                   // sei_cg_update: deepinv's `if rs_new.sqrt() < tol: break`
+        const float rs_new = *dst;
+        st->iterations += 1;
+        if (sqrtf(rs_new) < tol) {
+            st->done = 1;
+        } else {                                                 // ... else `p = r + p * (rs_new / rs); rs = rs_new`
+            st->beta = rs_new / st->rs;
+            st->rs = rs_new;
+        }
+    }
+}
+}  // namespace
+
+int sei_fold_cg(const float *part, int groups, SeiCgState *state, int target, float tol, hipStream_t s) {
+    SEI_REQUIRE(part && state && groups > 0 && target >= SEI_CG_FOLD_RS && target <= SEI_CG_FOLD_RS_NEW);
+    float *dst = target == SEI_CG_FOLD_RS ? &state->rs : target == SEI_CG_FOLD_PAP ? &state->pAp : &state->rs_new;
+    const SeiFoldJob job = sei_fold_job(SEI_FOLD_SPLIT, part, groups, 1, 1, dst, nullptr, nullptr);
+    hipLaunchKernelGGL(fold_cg_kernel, dim3(1), dim3(FOLD_SLICES * FOLD_ONE_E), 0, s, job, state, target, tol);
+    return sei_launch_status();
+}
 
 int sei_fold_now(const SeiFoldJob &job, hipStream_t s) {
     if (const int rc = fold_job_check(job)) return rc;

@@ -165,3 +165,9 @@ static inline SeiFoldJob sei_fold_job(int kind, const float *part, int groups, i
     J.part[0] = part; J.groups[0] = groups;
     return J;
 }
+// reduce_kernels.hip: the fold behind a reduction of the conjugate-gradient family (diffpir_kernels.hip) -- part[groups]
+// added in the order of fold_entries into one scalar of the device-resident state, by one workgroup that then keeps the
+// state's books (SeiCgState in include/sei_hip.h says which). Not exported.
+enum { SEI_CG_FOLD_RS = 0, SEI_CG_FOLD_PAP = 1, SEI_CG_FOLD_RS_NEW = 2 };
+__attribute__((visibility("hidden"))) int sei_fold_cg(const float *part, int groups, SeiCgState *state, int target, float tol,
+                                                      hipStream_t s);

@@ -14,8 +14,11 @@ the fused sei_dip_* kernels; parity with deepinv unpinned, the float64 restateme
 pinned truth; --dip_iterations, with the reference's defaults for deblurring and sr) and "PlugAndPlay" (models/pnp.py:
 DPIR half-quadratic splitting around the DRUNet of models/drunet.py on the fused sei_drunet_* kernels; the user names the
 pretrained weights with --drunet_weights, nothing is fetched; parity with deepinv unpinned, tests/drunet_ref.py is the
-pinned truth). The other test-time baselines (BM3D, DiffPIR, DPS) need pretrained networks or a package that is not here;
-they raise a clear error instead of silently running something else. (A second pretrained network sits outside this
+pinned truth) and "DiffPIR_DRUNet" (models/diffpir.py: deepinv's DiffPIR restated around the same DRUNet and the same
+--drunet_weights, its data step on the fused sei_cg_* conjugate-gradient kernels and its sampling step on
+sei_diffpir_sample; --diffpir_iterations, default 100; parity with deepinv unpinned, tests/diffpir_ref.py is the pinned
+truth). The other test-time baselines (BM3D, DiffPIR_DiffUNet, DPS) need a second pretrained network or a package that is
+not here; they raise a clear error instead of silently running something else. (A second pretrained network sits outside this
 factory: the AlexNet features of the LPIPS metric, metrics.LPIPS, five convolutions whose two small published weight files
 the user names to test.py.)
 """
@@ -28,12 +31,13 @@ from physics import _bands
 from physics._ops import SeparableResampleOp, apply_linear
 from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
+from .diffpir import DiffPIR
 from .dip import DeepImagePrior
 from .drunet import DRUNet
 from .pnp import PnPModel
 from .tv import TV
 
-_OUT_OF_SCOPE = ("BM3D", "DiffPIR_DRUNet", "DiffPIR_DiffUNet", "DPS")
+_OUT_OF_SCOPE = ("BM3D", "DiffPIR_DiffUNet", "DPS")
 
 
 class Identity(Module):
@@ -122,6 +126,16 @@ class Model(Module):
                                           "its state dict (KAIR's drunet_color.pth) with --drunet_weights")
             self.model = PnPModel(physics=physics, noise_level_img=noise_level / 255, early_stop=True,
                                   denoiser=DRUNet.from_file(weights, device))
+        elif kind == "DiffPIR_DRUNet":                        # reference :125-126 (its wrapper dies on this path: models/diffpir.py)
+            weights = blueprint[DiffPIR.__name__]["drunet_weights"]
+            if weights is None:
+                raise NotImplementedError("model kind 'DiffPIR_DRUNet' runs a pretrained DRUNet and nothing is fetched: name "
+                                          "its state dict (KAIR's drunet_color.pth) with --drunet_weights")
+            if physics is None:
+                raise NotImplementedError("model kind 'DiffPIR_DRUNet' solves its data step with the physics' A and "
+                                          "A_adjoint: it cannot run on a folder of measurements without a physics")
+            self.model = DiffPIR(physics=physics, denoiser=DRUNet.from_file(weights, device),
+                                 max_iter=blueprint[DiffPIR.__name__]["max_iter"])
         elif kind in _OUT_OF_SCOPE:
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
                                       "hot path this build implements")
@@ -192,6 +206,9 @@ def get_model(args, physics, device):
         # TV raises NotImplementedError naming the flag)
         DeepImagePrior.__name__: {"iterations": _dip_iterations(args) if args.model_kind == "DeepImagePrior" else None},
         PnPModel.__name__: {"drunet_weights": getattr(args, "drunet_weights", None)},
+        DiffPIR.__name__: {"drunet_weights": getattr(args, "drunet_weights", None),
+                           "max_iter": 100 if getattr(args, "diffpir_iterations", None) is None
+                           else args.diffpir_iterations},
         TV.__name__: {"lambd": getattr(args, "tv_lambd", None), "max_iter": getattr(args, "tv_max_iter", None) or 300},
     }
     return Model(blueprint=blueprint, physics=physics, device=device,

@@ -16,12 +16,15 @@ gradient on sei_tv_prox; without --tv_lambd it raises, the reference has no defa
 forward needs no autograd, so the reference's `dip` switch around no_grad has nothing to do here) and `--model_kind
 PlugAndPlay --drunet_weights FILE` (models/pnp.py: DPIR half-quadratic splitting, eight calls of the DRUNet of models/drunet.py
 on the sei_drunet_* kernels per image; FILE is the state dict of KAIR's drunet_color.pth, never fetched: without the flag it
-raises and names it). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
+raises and names it) and `--model_kind DiffPIR_DRUNet --drunet_weights FILE [--diffpir_iterations N]` (models/diffpir.py:
+deepinv's DiffPIR restated around the same DRUNet, N = 100 denoiser calls per image by default and between them the data
+step's conjugate gradients on the fused sei_cg_* kernels and the sampling step on sei_diffpir_sample; its noise comes from
+torch's generator, seeded above like everything else). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
 `SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. `--lpips_backbone FILE --lpips_linear FILE`
 (build-side addition; both or neither) name a torchvision AlexNet state dict and the LPIPS v0.1 `alex` linear layers: the
 `LPIPS:`, `LPIPS std:` and `LIPS:` fields then carry metrics.lpips_fn's values (the sei_lpips_* kernels); without them they
-print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: BM3D / DiffPIR / DPS baselines (pretrained
-networks or the bm3d package).
+print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: the BM3D / DiffPIR_DiffUNet / DPS
+baselines (a second pretrained network or the bm3d package).
 """
 import os
 import sys
@@ -65,6 +68,7 @@ def build_parser():
     flag("--lpips_backbone", type=str, default=None, metavar="FILE")                     # build-side addition
     flag("--lpips_linear", type=str, default=None, metavar="FILE")                       # build-side addition
     flag("--drunet_weights", type=str, default=None, metavar="FILE")                     # build-side addition
+    flag("--diffpir_iterations", type=int, default=100)                                  # build-side addition
     return parser
 
 
