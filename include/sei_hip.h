@@ -51,8 +51,9 @@ extern "C" {
  * --------------------------------------------------------------------------------------------- */
 
 /* ABI version of this header; sei_abi_version() returns the value the library was built with. Adding an entry point
- * is backward compatible and does not change it: sei_circ_filter_sep joined version 12 that way (a binding written
- * against an earlier 12 keeps working; one that needs the new symbol checks for it by name). */
+ * is backward compatible and does not change it: sei_circ_filter_sep, sei_blur_sep_circ_lds and sei_resample_sepband_lds
+ * joined version 12 that way (a binding written against an earlier 12 keeps working; one that needs a new symbol checks
+ * for it by name). */
 #define SEI_ABI_VERSION 12
 int sei_abi_version(void);
 /* Fills name[0..n) with the gfx target the code objects were built for ("gfx950"). */
@@ -79,9 +80,15 @@ int sei_graph_node_counts(void *graph, int *kernel_nodes, int *all_nodes);
  *   y[p,i,j] = sum_{a,b} tv[a]*th[b] * x[p, (i+a-kv/2) mod H, (j+b-kh/2) mod W]     (transpose=1)
  * tv (kv taps) and th (kh taps) are the rank-1 factors of the kernel (device pointers).
  * kv, kh <= 63.
+ * One workgroup stages a 64 x 64 output tile with its halo in LDS; from 37 taps per axis on that is more than 64 KiB, and
+ * the kernel's dynamic-LDS allowance is raised once per device on the first such call (see "Launches above 64 KiB of
+ * LDS" below).
+ * sei_blur_sep_circ_lds: the dynamic LDS bytes of the launch sei_blur_sep_circ would make for these taps and this image
+ * (host arithmetic, nothing is launched; the entry point sizes its launch with the same function); 0 where it refuses.
  * ------------------------------------------------------------------------------------------- */
 int sei_blur_sep_circ(const float *x, float *y, const float *tv, const float *th, int kv, int kh,
                       int planes, int H, int W, int transpose, void *stream);
+size_t sei_blur_sep_circ_lds(int kv, int kh, int H, int W);
 /* Non-separable kernels (loaded from a file, src/physics/__init__.py:20-22): k is (kv,kh) row-major. */
 int sei_blur_dense_circ(const float *x, float *y, const float *k, int kv, int kh, int planes,
                         int H, int W, int transpose, void *stream);
@@ -100,8 +107,11 @@ int sei_blur_dense_circ(const float *x, float *y, const float *k, int kv, int kh
  * result stays in LDS until the column pass has consumed it. Each output keeps four partial sums per pass.
  * Any H, W >= 1. SEI_ERR_TOO_LARGE when the workgroup's tiles exceed LDS (160 KiB): 512 x 512 fits (137 KiB), the
  * bound is 136 * (H + W) + 1 KiB <= 160 KiB up to the rounding of the extents to 4 / 8 / 32.
- * The one piece of state behind this entry point: above 64 KiB of LDS the kernel's dynamic-LDS allowance is raised once
- * per device (hipFuncSetAttribute, on the first such call; idempotent, one bit per device remembered).
+ * Launches above 64 KiB of LDS (sei_circ_filter_sep, sei_blur_sep_circ, sei_resample_sepband): the one piece of state
+ * behind these entry points. Above 64 KiB the kernel's dynamic-LDS allowance is raised once per device
+ * (hipFuncSetAttribute to the 160 KiB of a CU, on the first such call; idempotent, one bit per (kernel, device)
+ * remembered). That first call must be an eager one: a stream capture of such an extent comes after an eager call of
+ * the same entry point on that device.
  * ------------------------------------------------------------------------------------------- */
 int sei_circ_filter_sep(const float *x, float *y, const float *cv, const float *ch, int planes, int H, int W,
                         void *stream);
@@ -116,10 +126,18 @@ int sei_circ_filter_sep(const float *x, float *y, const float *cv, const float *
  * index lo[o] (entries beyond the band are zero-padded; lo is non-decreasing; lo[o]+nb may exceed
  * the input size only on zero weights). stepv/steph = max_o (lo[o+1]-lo[o]) of each axis (the
  * caller built the bands on the host and knows it); it bounds the LDS footprint of a tile.
+ * One workgroup stages the input footprint of a 16 x 32 output tile, ((tile - 1) * step + band) per axis, in LDS: a
+ * 1356 x 2040 photograph resized to 256 x 385 (step 6, band 22) takes 105 KiB, so the kernel's dynamic-LDS allowance is
+ * raised once per device on the first call above 64 KiB (see "Launches above 64 KiB of LDS" above). Where the footprint
+ * exceeds the 160 KiB of a CU (reductions by 8 and more) the output tile is halved, the wider footprint first, until it
+ * fits: SEI_ERR_TOO_LARGE only when the bands of a single output pixel do not.
+ * sei_resample_sepband_lds: the dynamic LDS bytes of the launch sei_resample_sepband would make (host arithmetic,
+ * nothing is launched; the entry point sizes its launch with the same function); 0 where it refuses.
  * ------------------------------------------------------------------------------------------- */
 int sei_resample_sepband(const float *x, float *y, int planes, int Hi, int Wi, int Ho, int Wo,
                          const float *wv, const int *lov, int nbv, int stepv,
                          const float *wh, const int *loh, int nbh, int steph, void *stream);
+size_t sei_resample_sepband_lds(int Hi, int Wi, int Ho, int Wo, int nbv, int stepv, int nbh, int steph);
 
 /* ---------------------------------------------------------------------------------------------
  * EI transform: per-image zoom-out by bicubic grid sampling with reflection.

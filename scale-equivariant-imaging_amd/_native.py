@@ -200,6 +200,8 @@ CG_STATE_WORDS, CG_DONE, CG_ITERATIONS = 8, 3, 4
 
 # size queries: return size_t, take no stream
 SIZE_QUERIES = {
+    "sei_blur_sep_circ_lds": [_I, _I, _I, _I],
+    "sei_resample_sepband_lds": [_I, _I, _I, _I, _I, _I, _I, _I],
     "sei_proposed_draws_max_numel": [],
     "sei_ssim_luma_work_floats": [_I, _I, _I],
     "sei_lpips_work_floats": [_I, _I, _I],

@@ -751,26 +751,14 @@ extern "C" int sei_conv3x3_bwd_weight(const float *x, const float *gy, float *gw
             // ~512 workgroups: every CU busy, few atomics per output
             const dim3 grid(sei_capped_grid(runs, (C3_THREADS / 32) * (int)sei_ceil_div(runs, (size_t)512 * 8), 65535));
             hipStream_t st = (hipStream_t)stream;
-            const int CSv = small_out ? Cout : Cin, lay = small_out ? (nchw_gy ? 1 : 0) : (nchw_x ? 1 : 0);
+            const int lay = small_out ? (nchw_gy ? 1 : 0) : (nchw_x ? 1 : 0);
 #define SEI_C3_WG(CS, OUT)                                                                                          \
     hipLaunchKernelGGL((conv3x3_wgrad_c32_kernel<CS, OUT>), grid, dim3(C3_THREADS), 0, st, x, gy, gw, gb, B, H, W, \
                        lay, nruns_row, (int)runs);                                                                  \
     return sei_launch_status();
-            if (small_out) {
-                switch (CSv) {
-                    case 1: SEI_C3_WG(1, true)
-                    case 2: SEI_C3_WG(2, true)
-                    case 3: SEI_C3_WG(3, true)
-                    default: SEI_C3_WG(4, true)
-                }
-            } else {
-                switch (CSv) {
-                    case 1: SEI_C3_WG(1, false)
-                    case 2: SEI_C3_WG(2, false)
-                    case 3: SEI_C3_WG(3, false)
-                    default: SEI_C3_WG(4, false)
-                }
-            }
+            // (the MFMA kernel above owns CS <= 3: only the four-channel small tensor reaches the lane kernel)
+            if (small_out) { SEI_C3_WG(4, true) }
+            SEI_C3_WG(4, false)
 #undef SEI_C3_WG
         }
     }

@@ -425,22 +425,65 @@ inline void blur_tiles(int H, int W, int kv, int kh, int &th, int &tw) {
 
 }  // namespace
 
+// By HIP's contract a launch with more than 64 KiB of dynamic LDS needs the kernel's allowance raised first. (The ROCm 7
+// runtime on an MI355X was seen to launch resample_sepband_kernel and blur_sep_circ_kernel at 66 to 153 KiB without it,
+// with right results; the code keeps to the contract, not to that.) It is raised once per device (to the 160 KiB of a
+// CU), on the first such call there -- an eager one, ahead of any capture of the same extent -- and remembered in one bit
+// per (kernel, device): idempotent, so a race between two first calls only repeats it.
+constexpr size_t LDS_DEFAULT = 64 * 1024, LDS_MAX = 160 * 1024;
+
+struct BigLdsKernel {
+    const void *kernel;
+    std::atomic<unsigned long long> devices{0};
+};
+static BigLdsKernel big_lds_blur_sep{reinterpret_cast<const void *>(blur_sep_circ_kernel)};
+static BigLdsKernel big_lds_resample{reinterpret_cast<const void *>(resample_sepband_kernel)};
+static BigLdsKernel big_lds_circ_filter{reinterpret_cast<const void *>(circ_filter_sep_kernel)};
+
+static int allow_big_lds(BigLdsKernel &k, size_t lds) {
+    if (lds <= LDS_DEFAULT) return 0;
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return (int)e;
+    const unsigned long long bit = 1ull << (device & 63);
+    if (k.devices.load(std::memory_order_relaxed) & bit) return 0;
+    e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
+    if (e != hipSuccess) return (int)e;
+    k.devices.fetch_or(bit, std::memory_order_relaxed);
+    return 0;
+}
+
+// The launch sei_blur_sep_circ makes: tile and dynamic LDS bytes (0: refused).
+struct BlurSepLaunch {
+    int tile_h, tile_w;
+    size_t lds;
+};
+static BlurSepLaunch blur_sep_launch(int kv, int kh, int H, int W) {
+    BlurSepLaunch l{0, 0, 0};
+    if (H <= 0 || W <= 0 || kv <= 0 || kh <= 0 || kv > MAX_TAPS || kh > MAX_TAPS) return l;
+    blur_tiles(H, W, kv, kh, l.tile_h, l.tile_w);
+    const int ih = l.tile_h + kv - 1, iw = l.tile_w + kh - 1;
+    const size_t lds = sizeof(float) * (128 + ((ih * iw + 3) & ~3) + (size_t)ih * l.tile_w);
+    if (lds <= LDS_MAX) l.lds = lds;
+    return l;
+}
+
+extern "C" size_t sei_blur_sep_circ_lds(int kv, int kh, int H, int W) { return blur_sep_launch(kv, kh, H, W).lds; }
+
 extern "C" int sei_blur_sep_circ(const float *x, float *y, const float *tv, const float *th, int kv,
                                  int kh, int planes, int H, int W, int transpose, void *stream) {
     SEI_REQUIRE(x && y && tv && th && x != y);
     SEI_REQUIRE(planes > 0 && H > 0 && W > 0 && kv > 0 && kh > 0);
-    if (kv > MAX_TAPS || kh > MAX_TAPS) return SEI_ERR_TOO_LARGE;
-    int tile_h, tile_w;
-    blur_tiles(H, W, kv, kh, tile_h, tile_w);
-    const int tiles_y = (int)sei_ceil_div(H, tile_h), tiles_x = (int)sei_ceil_div(W, tile_w);
-    const int ih = tile_h + kv - 1, iw = tile_w + kh - 1;
-    const size_t lds = sizeof(float) * (128 + ((ih * iw + 3) & ~3) + (size_t)ih * tile_w);
-    if (lds > 160 * 1024) return SEI_ERR_TOO_LARGE;
+    const BlurSepLaunch l = blur_sep_launch(kv, kh, H, W);
+    if (l.lds == 0) return SEI_ERR_TOO_LARGE;
+    const int tiles_y = (int)sei_ceil_div(H, l.tile_h), tiles_x = (int)sei_ceil_div(W, l.tile_w);
     // forward: shift kv/2, taps as given; adjoint: flipped taps, shift kv-1-kv/2
     const int sv = transpose ? kv - 1 - kv / 2 : kv / 2, sh = transpose ? kh - 1 - kh / 2 : kh / 2;
     const size_t grid = (size_t)planes * tiles_y * tiles_x;
-    hipLaunchKernelGGL(blur_sep_circ_kernel, dim3((unsigned)grid), dim3(BLUR_THREADS), lds, (hipStream_t)stream,
-                       x, y, tv, th, kv, kh, sv, sh, transpose ? 1 : 0, H, W, tile_h, tile_w, tiles_y, tiles_x);
+    const int rc = allow_big_lds(big_lds_blur_sep, l.lds);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(blur_sep_circ_kernel, dim3((unsigned)grid), dim3(BLUR_THREADS), l.lds, (hipStream_t)stream,
+                       x, y, tv, th, kv, kh, sv, sh, transpose ? 1 : 0, H, W, l.tile_h, l.tile_w, tiles_y, tiles_x);
     return sei_launch_status();
 }
 
@@ -453,7 +496,7 @@ extern "C" int sei_blur_dense_circ(const float *x, float *y, const float *k, int
     const int tiles_y = (int)sei_ceil_div(H, tile_h), tiles_x = (int)sei_ceil_div(W, tile_w);
     const int ih = tile_h + kv - 1, iw = tile_w + kh - 1;
     const size_t lds = sizeof(float) * (((kv * kh + 3) & ~3) + (size_t)ih * iw);
-    if (lds > 160 * 1024) return SEI_ERR_TOO_LARGE;
+    if (lds > LDS_MAX) return SEI_ERR_TOO_LARGE;
     const int sv = transpose ? kv - 1 - kv / 2 : kv / 2, sh = transpose ? kh - 1 - kh / 2 : kh / 2;
     const size_t grid = (size_t)planes * tiles_y * tiles_x;
     hipLaunchKernelGGL(blur_dense_circ_kernel, dim3((unsigned)grid), dim3(BLUR_THREADS), lds, (hipStream_t)stream,
@@ -468,41 +511,53 @@ static size_t circ_filter_lds(int H, int W) {
     return sizeof(float) * (len_h + len_v + (size_t)CF_ROWS * cf_stride(W4) + (size_t)CF_STRIP * cf_stride(H4));
 }
 
-// A launch with more than 64 KiB of dynamic LDS needs the kernel's allowance raised first. That is done once per device
-// (to the 160 KiB of a CU), on the first such call there -- an eager one, ahead of any capture of the same extent -- and
-// remembered in one bit per device: idempotent, so a race between two first calls only repeats it.
-static std::atomic<unsigned long long> cf_big_lds_devices{0};
-
-static int circ_filter_allow_big_lds() {
-    int device = 0;
-    hipError_t e = hipGetDevice(&device);
-    if (e != hipSuccess) return (int)e;
-    const unsigned long long bit = 1ull << (device & 63);
-    if (cf_big_lds_devices.load(std::memory_order_relaxed) & bit) return 0;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(circ_filter_sep_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    cf_big_lds_devices.fetch_or(bit, std::memory_order_relaxed);
-    return 0;
-}
-
 extern "C" int sei_circ_filter_sep(const float *x, float *y, const float *cv, const float *ch, int planes, int H,
                                    int W, void *stream) {
     SEI_REQUIRE(x && y && cv && ch && x != y);
     SEI_REQUIRE(planes > 0 && H > 0 && W > 0);
     if (H > (1 << 15) || W > (1 << 15)) return SEI_ERR_TOO_LARGE;
     const size_t lds = circ_filter_lds(H, W);
-    if (lds > 160 * 1024) return SEI_ERR_TOO_LARGE;
+    if (lds > LDS_MAX) return SEI_ERR_TOO_LARGE;
     const int strips = (int)sei_ceil_div(W, CF_STRIP);
     const size_t grid = (size_t)planes * strips;
     if (grid >= ((size_t)1 << 31)) return SEI_ERR_TOO_LARGE;
-    if (lds > 64 * 1024) {
-        const int rc = circ_filter_allow_big_lds();
-        if (rc != 0) return rc;
-    }
+    const int rc = allow_big_lds(big_lds_circ_filter, lds);
+    if (rc != 0) return rc;
     hipLaunchKernelGGL(circ_filter_sep_kernel, dim3((unsigned)grid), dim3(CF_THREADS), lds, (hipStream_t)stream, x, y,
                        cv, ch, H, W, strips);
     return sei_launch_status();
+}
+
+// The launch sei_resample_sepband makes: output tile, the LDS footprint bound of its input, dynamic LDS bytes (0: refused).
+// Output tile 16 x 32; its input footprint is at most (tile-1)*step + band per axis. Where that asks for more LDS than a
+// CU has (reductions by 8 and more), the tile is halved, the wider footprint first, until it fits.
+struct ResampleLaunch {
+    int tile_h, tile_w, fh_max, fw_max;
+    size_t lds;
+};
+static ResampleLaunch resample_launch(int Hi, int Wi, int Ho, int Wo, int nbv, int stepv, int nbh, int steph) {
+    ResampleLaunch l{0, 0, 0, 0, 0};
+    if (Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || nbv <= 0 || nbh <= 0 || stepv < 0 || steph < 0) return l;
+    l.tile_h = Ho < 16 ? Ho : 16;
+    l.tile_w = Wo < 32 ? Wo : 32;
+    for (;;) {
+        // (64-bit: a step is below the input extent, so a footprint bound is below 32 extents)
+        const long long fh = (long long)(l.tile_h - 1) * stepv + nbv, fw = (long long)(l.tile_w - 1) * steph + nbh;
+        l.fh_max = (int)(fh < Hi ? fh : Hi);
+        l.fw_max = (int)(fw < Wi ? fw : Wi);
+        const size_t lds = sizeof(float) * ((((size_t)l.fh_max * l.fw_max + 3) & ~(size_t)3) + (size_t)l.fh_max * l.tile_w);
+        if (lds <= LDS_MAX) {
+            l.lds = lds;
+            return l;
+        }
+        if (l.tile_w > 1 && (l.fw_max >= l.fh_max || l.tile_h == 1)) l.tile_w = (l.tile_w + 1) / 2;
+        else if (l.tile_h > 1) l.tile_h = (l.tile_h + 1) / 2;
+        else return l;                                  // one output pixel's own bands do not fit
+    }
+}
+
+extern "C" size_t sei_resample_sepband_lds(int Hi, int Wi, int Ho, int Wo, int nbv, int stepv, int nbh, int steph) {
+    return resample_launch(Hi, Wi, Ho, Wo, nbv, stepv, nbh, steph).lds;
 }
 
 extern "C" int sei_resample_sepband(const float *x, float *y, int planes, int Hi, int Wi, int Ho, int Wo,
@@ -511,18 +566,16 @@ extern "C" int sei_resample_sepband(const float *x, float *y, int planes, int Hi
     SEI_REQUIRE(x && y && wv && lov && wh && loh && x != y);
     SEI_REQUIRE(planes > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && nbv > 0 && nbh > 0);
     SEI_REQUIRE(stepv >= 0 && steph >= 0);
-    // Output tile 16 x 32; its input footprint is at most (tile-1)*step + band per axis.
-    const int tile_h = Ho < 16 ? Ho : 16, tile_w = Wo < 32 ? Wo : 32;
-    int fh_max = (tile_h - 1) * stepv + nbv, fw_max = (tile_w - 1) * steph + nbh;
-    if (fh_max > Hi) fh_max = Hi;
-    if (fw_max > Wi) fw_max = Wi;
-    const size_t lds = sizeof(float) * (((size_t)(fh_max * fw_max + 3) & ~(size_t)3) + (size_t)fh_max * tile_w);
-    if (lds > 160 * 1024) return SEI_ERR_TOO_LARGE;
-    const int tiles_y = (int)sei_ceil_div(Ho, tile_h), tiles_x = (int)sei_ceil_div(Wo, tile_w);
+    const ResampleLaunch l = resample_launch(Hi, Wi, Ho, Wo, nbv, stepv, nbh, steph);
+    if (l.lds == 0) return SEI_ERR_TOO_LARGE;
+    const int tiles_y = (int)sei_ceil_div(Ho, l.tile_h), tiles_x = (int)sei_ceil_div(Wo, l.tile_w);
     const size_t grid = (size_t)planes * tiles_y * tiles_x;
-    hipLaunchKernelGGL(resample_sepband_kernel, dim3((unsigned)grid), dim3(RS_THREADS), lds, (hipStream_t)stream,
-                       x, y, Hi, Wi, Ho, Wo, wv, lov, nbv, wh, loh, nbh, tile_h, tile_w, tiles_y, tiles_x,
-                       fh_max, fw_max);
+    if (grid >= ((size_t)1 << 31)) return SEI_ERR_TOO_LARGE;
+    const int rc = allow_big_lds(big_lds_resample, l.lds);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(resample_sepband_kernel, dim3((unsigned)grid), dim3(RS_THREADS), l.lds, (hipStream_t)stream,
+                       x, y, Hi, Wi, Ho, Wo, wv, lov, nbv, wh, loh, nbh, l.tile_h, l.tile_w, tiles_y, tiles_x,
+                       l.fh_max, l.fw_max);
     return sei_launch_status();
 }
 

@@ -789,3 +789,35 @@ def test_shadow_state_decides_when_a_bf16_copy_is_current():
     assert "consolidate()" in str(a.stale_error())
     a.set_stale(None)
     assert a.stale is None and not a.stale_overlaps(p) and not a.stale_overlaps(q)
+
+
+def test_lds_queries_of_the_resampler_and_the_separable_blur():
+    """sei_resample_sepband_lds / sei_blur_sep_circ_lds: the dynamic LDS bytes of the launch the entry point would make
+    (host arithmetic; the entry points size their launches with the same functions), 0 where it refuses. A DIV2K
+    photograph resized as GroundTruthDataset does takes 105 KiB -- above the 64 KiB a kernel is launched with by default
+    -- and a reduction by 8 halves its output tile instead of refusing."""
+    import _native
+    from physics import _bands
+    L = _native.lib()
+
+    def resample_lds(hi, wi, ho, wo):
+        _, _, nbv, sv = _bands.to_band(_bands.aa_bicubic_matrix_to_size(hi, ho))
+        _, _, nbh, sh = _bands.to_band(_bands.aa_bicubic_matrix_to_size(wi, wo))
+        return (sv, nbv, sh, nbh), L.sei_resample_sepband_lds(hi, wi, ho, wo, nbv, sv, nbh, sh)
+
+    assert resample_lds(1356, 2040, 256, 385) == ((6, 22, 6, 22), 107520)       # 112 x 208 footprint + 112 x 32 rows
+    assert resample_lds(300, 421, 214, 300)[1] < 65536
+    band, lds = resample_lds(260, 530, 33, 67)                                  # 152 x 280: 185 KiB with the 16 x 32 tile
+    assert band == (8, 32, 8, 32) and lds == 4 * (152 * 152 + 152 * 16)         # ... the tile halved to 16 x 16
+    assert L.sei_resample_sepband_lds(4000, 4000, 16, 32, 150, 250, 150, 250) == 4 * (150 * 150 + 150 * 1)   # down to 1 x 1
+    assert L.sei_resample_sepband_lds(4000, 4000, 16, 32, 150, 250, 3000, 250) == 0     # one pixel's bands: 1.7 MiB
+    assert L.sei_resample_sepband_lds(0, 8, 4, 4, 2, 1, 2, 1) == 0 and L.sei_resample_sepband_lds(8, 8, 4, 4, 0, 1, 2, 1) == 0
+    assert L.sei_resample_sepband(16, 32, 1, 4000, 4000, 16, 32, 48, 64, 150, 250, 80, 96, 3000, 250, None) == 10002
+
+    assert L.sei_blur_sep_circ_lds(63, 63, 64, 64) == 96272                     # 128 + 126 x 126 + 126 x 64 floats
+    assert L.sei_blur_sep_circ_lds(19, 19, 256, 256) < 65536
+    assert L.sei_blur_sep_circ_lds(36, 36, 64, 64) < 65536 < L.sei_blur_sep_circ_lds(37, 37, 64, 64)
+    assert L.sei_blur_sep_circ_lds(63, 63, 5, 7) == 4 * (128 + ((67 * 69 + 3) & ~3) + 67 * 7)
+    assert L.sei_blur_sep_circ_lds(64, 3, 64, 64) == 0 and L.sei_blur_sep_circ_lds(3, 64, 64, 64) == 0
+    assert L.sei_blur_sep_circ_lds(0, 3, 64, 64) == 0 and L.sei_blur_sep_circ_lds(3, 3, 0, 64) == 0
+    assert L.sei_blur_sep_circ(16, 32, 48, 64, 64, 3, 1, 64, 64, 0, None) == 10002
