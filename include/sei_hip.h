@@ -36,7 +36,8 @@ extern "C" {
  * ctypes stub for each at its reference call site); names, argument meaning and error behaviour are kept across ABI
  * versions:
  *   sei_abi_version, sei_build_target
- *   physics      sei_blur_sep_circ, sei_blur_dense_circ, sei_resample_sepband, sei_circ_filter_sep
+ *   physics      sei_blur_sep_circ, sei_blur_dense_circ, sei_blur_dense_pad (+ _work_floats), sei_resample_sepband,
+ *                sei_circ_filter_sep
  *   EI transform sei_scale_resample_fwd, sei_scale_resample_bwd
  *   loss terms   sei_axpy, sei_sure_terms, sei_mse_terms
  *   U-Net (f32)  sei_conv3x3_fwd, sei_conv3x3_bwd_weight, sei_dwconv7_fwd, sei_dwconv7_bwd_weight (+ _workspace),
@@ -51,8 +52,8 @@ extern "C" {
  * --------------------------------------------------------------------------------------------- */
 
 /* ABI version of this header; sei_abi_version() returns the value the library was built with. Adding an entry point
- * is backward compatible and does not change it: sei_circ_filter_sep, sei_blur_sep_circ_lds and sei_resample_sepband_lds
- * joined version 12 that way (a binding written against an earlier 12 keeps working; one that needs a new symbol checks
+ * is backward compatible and does not change it: sei_circ_filter_sep, sei_blur_sep_circ_lds, sei_resample_sepband_lds,
+ * sei_blur_dense_pad and sei_blur_dense_pad_work_floats joined version 12 that way (a binding written against an earlier 12 keeps working; one that needs a new symbol checks
  * for it by name). */
 #define SEI_ABI_VERSION 12
 int sei_abi_version(void);
@@ -92,6 +93,29 @@ size_t sei_blur_sep_circ_lds(int kv, int kh, int H, int W);
 /* Non-separable kernels (loaded from a file, src/physics/__init__.py:20-22): k is (kv,kh) row-major. */
 int sei_blur_dense_circ(const float *x, float *y, const float *k, int kv, int kh, int planes,
                         int H, int W, int transpose, void *stream);
+
+/* The legacy Blur's other boundaries (src/physics/blur/__init__.py:34-161, conv / conv_transpose with padding
+ * 'replicate', 'reflect', 'valid') for non-separable kernels; k is (kv,kh) row-major, H x W the IMAGE's extents in both
+ * directions. mode: 1 replicate, 2 reflect, 3 valid (0, circular, is SEI_ERR_BAD_ARG: sei_blur_dense_circ is the circular
+ * route). Per axis of K taps and image length n, (s, p) = (K/2, K/2) for odd K >= 3, (K/2 - 1, K/2) for even K, (0, 1)
+ * for K = 1 (the reference flips the filter and zero-extends it to an odd length, at least 3):
+ *   same-size modes  y[i]  = sum_a c[a] x[map(i - a + s)],     map(e) = min(max(e, 0), n-1)                   (replicate)
+ *                                                              map(e) = e < 0 ? -e : e > n-1 ? 2(n-1) - e : e (reflect; needs
+ *                                                              p <= n-1, SEI_ERR_BAD_ARG otherwise)
+ *   valid            y[i'] = sum_a c[a] x[i' + p - a + s],     i' in [0, n - 2p)   (needs n > 2p, SEI_ERR_BAD_ARG otherwise)
+ * in two dimensions the tensor product of the two axis rules applied to k[a,b]; y is (planes, H - 2pv, W - 2ph) in valid.
+ * transpose = 1: the exact transpose (x is then the measurement-sized image -- the cropped one in valid -- and y is
+ * H x W): out[u,v] = sum of Z[e,f] over the positions (e,f), e in [-pv, H-1+pv], f in [-ph, W-1+ph], that the two axis
+ * maps send to (u,v), where Z[e,f] = sum_{a,b} k[a,b] x[e + a - sv, f + b - sh] with x zero outside its extent. Two
+ * launches: Z into `work`, then a gather per output in a fixed order (no atomics: the same bits on every run); valid has
+ * one preimage per position and is one launch, Z written straight to y.
+ * sei_blur_dense_pad_work_floats: the floats `work` must hold: planes (H + 2pv) (W + 2ph) for the transposes of
+ * replicate and reflect, 0 otherwise (work may then be NULL) -- and 0 for arguments the entry point refuses.
+ * Limits as sei_blur_dense_circ: taps <= 63 per axis (SEI_ERR_TOO_LARGE beyond; a tile with its halo then fits 64 KiB of
+ * LDS). SEI_ERR_BAD_ARG also on NULL pointers and when y or work overlap another operand. */
+int sei_blur_dense_pad(const float *x, float *y, const float *k, int kv, int kh, int planes, int H, int W, int mode,
+                       int transpose, float *work, void *stream);
+size_t sei_blur_dense_pad_work_floats(int planes, int H, int W, int kv, int kh, int mode, int transpose);
 
 /* ---------------------------------------------------------------------------------------------
  * Physics: separable dense circular filter  y[p] = C_v * x[p] * C_h^T  with full circulants

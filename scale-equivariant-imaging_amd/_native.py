@@ -31,6 +31,7 @@ SIGNATURES = {
     "sei_build_target": [_c.c_char_p, _I],
     "sei_blur_sep_circ": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sei_blur_dense_circ": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sei_blur_dense_pad": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "sei_circ_filter_sep": [_P, _P, _P, _P, _I, _I, _I, _P],
     "sei_resample_sepband": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P],
     "sei_scale_params": [_P, _P, _P, _I, _I, _P, _P, _P],
@@ -201,6 +202,7 @@ CG_STATE_WORDS, CG_DONE, CG_ITERATIONS = 8, 3, 4
 # size queries: return size_t, take no stream
 SIZE_QUERIES = {
     "sei_blur_sep_circ_lds": [_I, _I, _I, _I],
+    "sei_blur_dense_pad_work_floats": [_I, _I, _I, _I, _I, _I, _I],
     "sei_resample_sepband_lds": [_I, _I, _I, _I, _I, _I, _I, _I],
     "sei_proposed_draws_max_numel": [],
     "sei_ssim_luma_work_floats": [_I, _I, _I],
@@ -259,7 +261,9 @@ def lib():
             fn.argtypes = argtypes
             fn.restype = _I
         for name, argtypes in SIZE_QUERIES.items():
-            fn = getattr(handle, name)
+            fn = getattr(handle, name, None)
+            if fn is None:
+                continue            # (an earlier build of this ABI given through SEI_HIP_LIBRARY)
             fn.argtypes = argtypes
             fn.restype = _Z
         if handle.sei_abi_version() != ABI_VERSION:

@@ -5,7 +5,9 @@
 // Algorithmic bytes per plane: 4*H*W in + 4*Ho*Wo out.
 //
 //   sei_blur_sep_circ / sei_blur_dense_circ : BlurV2.A and its adjoint  (blur/__init__.py:205-227)
-//   sei_resample_sepband                    : Downsampling.A, adjoints, AA prefilter
+//   sei_blur_dense_pad                      : the legacy Blur's replicate / reflect / valid boundaries, both directions
+//                                             (blur/__init__.py:34-161), for kernels that are not rank one
+//   sei_resample_sepband                    : Downsampling.A, adjoints, AA prefilter; rank-one blurs with those boundaries
 //   sei_scale_resample_fwd/bwd              : padded_downsampling_transform (transforms.py:27-83)
 //   sei_circ_filter_sep                     : CTLikeFilter.A / A_dagger / filter1d (physics/ct_like_filter.py:10-39)
 //
@@ -108,6 +110,112 @@ __global__ __launch_bounds__(BLUR_THREADS) void blur_dense_circ_kernel(
             yp[(size_t)(i0 + r) * W + j0 + c] = acc;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// dense blur with a replicate / reflect / valid boundary (reference Blur: conv / conv_transpose,
+// src/physics/blur/__init__.py:34-161). The tiling of blur_dense_circ_kernel with the staging index map as a template
+// parameter and separate input and output extents:
+//   y[i,j] = sum_{a,b} k'[a,b] in[map(i - a + Sv), map(j - b + Sh)],   i < Ho, j < Wo,   k' = k or k flipped
+// PAD_ZERO reads 0 outside the input: the zero-boundary correlation Z of the adjoint (flipped taps, the output the input
+// extended by the padding on every side). Each tap row is summed on its own and the rows are then added in order: a
+// fixed order, and the rounding error of kh + kv additions instead of kv * kh.
+// ------------------------------------------------------------------------------------------------
+enum { PAD_REPLICATE = 1, PAD_REFLECT = 2, PAD_VALID = 3, PAD_ZERO = 4 };
+
+template <int MODE>
+__device__ __forceinline__ float pad_fetch(const float *__restrict__ xp, int e, int f, int H, int W) {
+    if (MODE == PAD_ZERO) return (e >= 0 && e < H && f >= 0 && f < W) ? xp[(size_t)e * W + f] : 0.f;
+    if (MODE == PAD_REFLECT) {
+        e = e < 0 ? -e : e;
+        e = e > H - 1 ? 2 * (H - 1) - e : e;
+        f = f < 0 ? -f : f;
+        f = f > W - 1 ? 2 * (W - 1) - f : f;
+    }
+    // the replicate rule. For the other two it only keeps the halo of a partial last tile inside the plane: their own
+    // rule leaves every position that feeds a written output in range already.
+    e = min(max(e, 0), H - 1);
+    f = min(max(f, 0), W - 1);
+    return xp[(size_t)e * W + f];
+}
+
+template <int MODE>
+__global__ __launch_bounds__(BLUR_THREADS) void blur_dense_pad_kernel(
+    const float *__restrict__ x, float *__restrict__ y, const float *__restrict__ k, int kv, int kh,
+    int sv, int sh, int flip, int Hi, int Wi, int Ho, int Wo, int tile_h, int tile_w, int tiles_y, int tiles_x) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x;
+    const int tiles = tiles_y * tiles_x;
+    const int plane = blockIdx.x / tiles;
+    const int t = blockIdx.x - plane * tiles;
+    const int i0 = (t / tiles_x) * tile_h, j0 = (t % tiles_x) * tile_w;
+    const int ih = tile_h + kv - 1, iw = tile_w + kh - 1;
+    const int nk = kv * kh;
+    float *s_k = smem;
+    float *s_in = smem + ((nk + 3) & ~3);
+    for (int idx = tid; idx < nk; idx += BLUR_THREADS) s_k[idx] = k[flip ? nk - 1 - idx : idx];
+    const float *xp = x + (size_t)plane * Hi * Wi;
+    const int r0 = i0 - kv + 1 + sv, c0 = j0 - kh + 1 + sh;
+    for (int idx = tid; idx < ih * iw; idx += BLUR_THREADS) {
+        const int r = idx / iw, l = idx - r * iw;
+        s_in[idx] = pad_fetch<MODE>(xp, r0 + r, c0 + l, Hi, Wi);
+    }
+    __syncthreads();
+    float *yp = y + (size_t)plane * Ho * Wo;
+    for (int idx = tid; idx < tile_h * tile_w; idx += BLUR_THREADS) {
+        const int r = idx / tile_w, c = idx - r * tile_w;
+        if (i0 + r < Ho && j0 + c < Wo) {
+            float acc = 0.f;
+            for (int a = 0; a < kv; ++a) {
+                const float *src = s_in + (r + kv - 1 - a) * iw + c + kh - 1;
+                float row = 0.f;
+                for (int b = 0; b < kh; ++b) row = fmaf(s_k[a * kh + b], src[-b], row);
+                acc += row;
+            }
+            yp[(size_t)(i0 + r) * Wo + j0 + c] = acc;
+        }
+    }
+}
+
+// The adjoint's fold: out[u,v] = sum of Z over the positions (e,f) of the extended canvas, e in [-pv, H-1+pv],
+// f in [-ph, W-1+ph], that the axis maps send to (u,v). One thread per output, a gather in a fixed order (rows outer,
+// columns inner; reflect: the pixel itself, its mirror about 0, its mirror about n-1): no atomics.
+__device__ __forceinline__ int reflect_preimages(int u, int n, int p, int e[3]) {
+    int m = 0;
+    e[m++] = u;
+    if (u >= 1 && u <= p) e[m++] = -u;
+    if (u < n - 1 && n - 1 - u <= p) e[m++] = 2 * (n - 1) - u;
+    return m;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void blur_pad_fold_kernel(const float *__restrict__ Z, float *__restrict__ out, int H,
+                                                            int W, int pv, int ph, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int v = (int)(idx % W);
+    const size_t q = idx / W;
+    const int u = (int)(q % H);
+    const size_t plane = q / H;
+    const int Wz = W + 2 * ph;
+    const float *zp = Z + plane * (size_t)(H + 2 * pv) * Wz;
+    float acc = 0.f;
+    if (MODE == PAD_REPLICATE) {
+        const int e0 = u == 0 ? -pv : u, e1 = u == H - 1 ? H - 1 + pv : u;
+        const int f0 = v == 0 ? -ph : v, f1 = v == W - 1 ? W - 1 + ph : v;
+        for (int e = e0; e <= e1; ++e) {
+            const float *zr = zp + (size_t)(e + pv) * Wz + ph;
+            for (int f = f0; f <= f1; ++f) acc += zr[f];
+        }
+    } else {
+        int ev[3], fv[3];
+        const int ne = reflect_preimages(u, H, pv, ev), nf = reflect_preimages(v, W, ph, fv);
+        for (int a = 0; a < ne; ++a) {
+            const float *zr = zp + (size_t)(ev[a] + pv) * Wz + ph;
+            for (int b = 0; b < nf; ++b) acc += zr[fv[b]];
+        }
+    }
+    out[idx] = acc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -501,6 +609,110 @@ extern "C" int sei_blur_dense_circ(const float *x, float *y, const float *k, int
     const size_t grid = (size_t)planes * tiles_y * tiles_x;
     hipLaunchKernelGGL(blur_dense_circ_kernel, dim3((unsigned)grid), dim3(BLUR_THREADS), lds, (hipStream_t)stream,
                        x, y, k, kv, kh, sv, sh, transpose ? 1 : 0, H, W, tile_h, tile_w, tiles_y, tiles_x);
+    return sei_launch_status();
+}
+
+// The launches sei_blur_dense_pad makes. One axis of K taps reads s positions before its output and K-1-s after it, of
+// an image padded by p: (K/2, K/2) for odd K >= 3, (K/2 - 1, K/2) for even K, (0, 1) for K = 1 (sei_hip.h).
+struct BlurPadPlan {
+    int Hi, Wi, Ho, Wo;      // extents the tiled kernel reads and writes (its output is Z when `fold`)
+    int sv, sh, flip, stage; // shifts, tap order and staging map of the tiled kernel
+    int pv, ph;
+    bool fold;
+    size_t work;             // floats of Z (0: the tiled kernel writes y)
+};
+static void blur_pad_axis(int K, int &s, int &p) {
+    if (K == 1) s = 0, p = 1;
+    else if (K & 1) s = p = K / 2;
+    else s = K / 2 - 1, p = K / 2;
+}
+static int blur_pad_plan(int planes, int H, int W, int kv, int kh, int mode, int transpose, BlurPadPlan &pl) {
+    SEI_REQUIRE(planes > 0 && H > 0 && W > 0 && kv > 0 && kh > 0);
+    SEI_REQUIRE(mode == PAD_REPLICATE || mode == PAD_REFLECT || mode == PAD_VALID);
+    if (kv > MAX_TAPS || kh > MAX_TAPS || H > (1 << 30) || W > (1 << 30)) return SEI_ERR_TOO_LARGE;
+    int sv, sh;
+    blur_pad_axis(kv, sv, pl.pv);
+    blur_pad_axis(kh, sh, pl.ph);
+    if (mode == PAD_REFLECT) SEI_REQUIRE(pl.pv <= H - 1 && pl.ph <= W - 1);
+    if (mode == PAD_VALID) SEI_REQUIRE(H > 2 * pl.pv && W > 2 * pl.ph);
+    pl.Hi = pl.Ho = H, pl.Wi = pl.Wo = W;
+    pl.fold = false, pl.work = 0;
+    if (!transpose) {
+        pl.flip = 0, pl.stage = mode;
+        pl.sv = sv, pl.sh = sh;
+        if (mode == PAD_VALID) pl.Ho = H - 2 * pl.pv, pl.Wo = W - 2 * pl.ph, pl.sv += pl.pv, pl.sh += pl.ph;
+    } else {
+        pl.flip = 1, pl.stage = PAD_ZERO;
+        pl.sv = kv - 1 - pl.pv - sv, pl.sh = kh - 1 - pl.ph - sh;
+        if (mode == PAD_VALID) {
+            pl.Hi = H - 2 * pl.pv, pl.Wi = W - 2 * pl.ph;    // Z of the cropped image is the whole result
+        } else {
+            pl.Ho = H + 2 * pl.pv, pl.Wo = W + 2 * pl.ph;
+            pl.fold = true;
+            pl.work = (size_t)planes * pl.Ho * pl.Wo;
+        }
+    }
+    const size_t tiles = sei_ceil_div(pl.Ho, 32) * sei_ceil_div(pl.Wo, 64);
+    if ((size_t)planes * tiles >= ((size_t)1 << 31) || sei_ceil_div((size_t)planes * H * W, 256) >= ((size_t)1 << 31))
+        return SEI_ERR_TOO_LARGE;
+    return 0;
+}
+
+static bool floats_overlap(const float *a, size_t na, const float *b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
+}
+
+template <int MODE>
+static void blur_dense_pad_launch(const float *x, float *y, const float *k, int kv, int kh, int planes,
+                                  const BlurPadPlan &pl, hipStream_t stream) {
+    const int tile_h = pl.Ho < 32 ? pl.Ho : 32, tile_w = pl.Wo < 64 ? pl.Wo : 64;
+    const int tiles_y = (int)sei_ceil_div(pl.Ho, tile_h), tiles_x = (int)sei_ceil_div(pl.Wo, tile_w);
+    const int ih = tile_h + kv - 1, iw = tile_w + kh - 1;
+    const size_t lds = sizeof(float) * (((kv * kh + 3) & ~3) + (size_t)ih * iw);      // <= 63 KiB at 63 x 63 taps
+    const size_t grid = (size_t)planes * tiles_y * tiles_x;
+    hipLaunchKernelGGL(blur_dense_pad_kernel<MODE>, dim3((unsigned)grid), dim3(BLUR_THREADS), lds, stream, x, y, k, kv, kh,
+                       pl.sv, pl.sh, pl.flip, pl.Hi, pl.Wi, pl.Ho, pl.Wo, tile_h, tile_w, tiles_y, tiles_x);
+}
+
+extern "C" size_t sei_blur_dense_pad_work_floats(int planes, int H, int W, int kv, int kh, int mode, int transpose) {
+    BlurPadPlan pl;
+    return blur_pad_plan(planes, H, W, kv, kh, mode, transpose, pl) == 0 ? pl.work : 0;
+}
+
+extern "C" int sei_blur_dense_pad(const float *x, float *y, const float *k, int kv, int kh, int planes, int H, int W,
+                                  int mode, int transpose, float *work, void *stream) {
+    SEI_REQUIRE(x && y && k);
+    BlurPadPlan pl;
+    const int rc = blur_pad_plan(planes, H, W, kv, kh, mode, transpose, pl);
+    if (rc != 0) return rc;
+    SEI_REQUIRE(pl.work == 0 || work);
+    // x and y at the image's extent or, in `valid`, the cropped one on the side the direction puts it
+    const size_t full = (size_t)planes * H * W, crop = (size_t)planes * (H - 2 * pl.pv) * (W - 2 * pl.ph);
+    const size_t nx = mode == PAD_VALID && transpose ? crop : full, ny = mode == PAD_VALID && !transpose ? crop : full;
+    const size_t nk = (size_t)kv * kh;
+    SEI_REQUIRE(!floats_overlap(x, nx, y, ny) && !floats_overlap(k, nk, y, ny));
+    if (pl.work) SEI_REQUIRE(!floats_overlap(x, nx, work, pl.work) && !floats_overlap(y, ny, work, pl.work) &&
+                             !floats_overlap(k, nk, work, pl.work));
+    hipStream_t s = (hipStream_t)stream;
+    float *dst = pl.fold ? work : y;
+    switch (pl.stage) {
+    case PAD_REPLICATE: blur_dense_pad_launch<PAD_REPLICATE>(x, dst, k, kv, kh, planes, pl, s); break;
+    case PAD_REFLECT: blur_dense_pad_launch<PAD_REFLECT>(x, dst, k, kv, kh, planes, pl, s); break;
+    case PAD_VALID: blur_dense_pad_launch<PAD_VALID>(x, dst, k, kv, kh, planes, pl, s); break;
+    default: blur_dense_pad_launch<PAD_ZERO>(x, dst, k, kv, kh, planes, pl, s); break;
+    }
+    if (pl.fold) {
+        const int status = sei_launch_status();
+        if (status != 0) return status;
+        const unsigned grid = (unsigned)sei_ceil_div(full, 256);
+        if (mode == PAD_REPLICATE)
+            hipLaunchKernelGGL(blur_pad_fold_kernel<PAD_REPLICATE>, dim3(grid), dim3(256), 0, s, work, y, H, W, pl.pv, pl.ph,
+                               full);
+        else
+            hipLaunchKernelGGL(blur_pad_fold_kernel<PAD_REFLECT>, dim3(grid), dim3(256), 0, s, work, y, H, W, pl.pv, pl.ph,
+                               full);
+    }
     return sei_launch_status();
 }
 

@@ -32,10 +32,14 @@ class BlurKernel:
 
 
 class PhysicsManager:
-    def __init__(self, blueprint, task, device, noise_level, v2):
+    def __init__(self, blueprint, task, device, noise_level, v2, blur_padding="circular"):
         if task == "deblurring":
             kernel = BlurKernel(**blueprint[BlurKernel.__name__]).to_tensor(device)
-            physics = BlurV2(kernel=kernel) if v2 else Blur(filter=kernel, padding="circular", device=device)
+            # (the FFT operator BlurV2 stands for has no boundary but the circular one)
+            if v2 and blur_padding == "circular":
+                physics = BlurV2(kernel=kernel)
+            else:
+                physics = Blur(filter=kernel, padding=blur_padding, device=device)
         elif task == "sr":
             physics = Downsampling(antialias=True, **blueprint[Downsampling.__name__])
         elif task == "invert_a_tomography_like_filter":
@@ -62,7 +66,8 @@ class PhysicsManager:
 
 def get_physics(args, device):
     blueprint = {
-        PhysicsManager.__name__: {"task": args.task, "noise_level": args.noise_level, "v2": args.physics_v2},
+        PhysicsManager.__name__: {"task": args.task, "noise_level": args.noise_level, "v2": args.physics_v2,
+                                   "blur_padding": getattr(args, "blur_padding", "circular")},
         BlurKernel.__name__: {"kernel_path": args.kernel},
         Downsampling.__name__: {"rate": args.sr_factor, "true_adjoint": args.physics_true_adjoint},
     }

@@ -92,6 +92,57 @@ def plain_bicubic_matrix_to_size(n_in, n_out):
     return m
 
 
+BLUR_PADDINGS = ("circular", "replicate", "reflect", "valid")
+
+
+def blur_axis_offsets(K):
+    """(s, p) of one axis of the legacy Blur with K taps: output i reads positions i - a + s, a in [0, K), of an image
+    padded by p on each side. The reference (src/physics/blur/__init__.py:9-62) flips the filter, zero-extends an even
+    length by one at the end and a single tap to three, and pads by half the extended length."""
+    if K < 1:
+        raise ValueError(f"blur: a filter axis needs at least one tap, got {K}")
+    if K == 1:
+        return 0, 1
+    if K % 2:
+        return K // 2, K // 2
+    return K // 2 - 1, K // 2
+
+
+def blur_axis_matrix(n, taps, mode):
+    """Dense float64 (n_out, n) matrix of one axis of Blur(padding=mode) on an image of length n, literally
+    y[i] = sum_a taps[a] x[map(i - a + s)]: map is e mod n (circular), the clamp to [0, n-1] (replicate) or the mirror
+    about 0 and n-1 (reflect; needs p <= n-1, as torch's pad does). valid: y[i'] = sum_a taps[a] x[i' + p - a + s] for i'
+    in [0, n - 2p), which needs n > 2p. In two dimensions the operator is M_v x M_h^T, its adjoint M_v^T g M_h."""
+    c = np.asarray(taps, dtype=np.float64).reshape(-1)
+    K = c.size
+    s, p = blur_axis_offsets(K)
+    if mode not in BLUR_PADDINGS:
+        raise ValueError(f"blur: padding must be one of {BLUR_PADDINGS}, got {mode!r}")
+    if mode == "valid":
+        if n <= 2 * p:
+            raise ValueError(f"blur: padding='valid' needs an extent above {2 * p} for a kernel of {K} taps, got {n}")
+        m = np.zeros((n - 2 * p, n))
+        for i in range(n - 2 * p):
+            for a in range(K):
+                m[i, i + p - a + s] += c[a]
+        return m
+    if mode == "reflect" and p > n - 1:
+        raise ValueError(f"blur: padding='reflect' pads by {p} for a kernel of {K} taps, which an extent of {n} "
+                         f"cannot mirror (it needs an extent of at least {p + 1})")
+    m = np.zeros((n, n))
+    for i in range(n):
+        for a in range(K):
+            e = i - a + s
+            if mode == "circular":
+                e %= n
+            elif mode == "replicate":
+                e = min(max(e, 0), n - 1)
+            else:
+                e = -e if e < 0 else 2 * (n - 1) - e if e > n - 1 else e
+            m[i, e] += c[a]
+    return m
+
+
 def to_band(dense):
     """Dense (n_out, n_in) -> (weights (n_out, nb) f32, lo (n_out,) i32, nb, max step of lo).
     Band starts are made non-decreasing (a row whose leading weights are exact zeros of the cubic

@@ -73,6 +73,79 @@ class CircularBlurOp:
         return y
 
 
+class PaddedBlurOp:
+    """y = k (*) x with a replicate, reflect or valid boundary (reference Blur: conv / conv_transpose,
+    src/physics/blur/__init__.py:34-161; the axis rule is physics/_bands.blur_axis_matrix). Rank-1 kernels (the rank-1
+    test of CircularBlurOp) run as two banded axis matrices through SeparableResampleOp, which transposes exactly and
+    takes the rectangular `valid`; anything else runs sei_blur_dense_pad. Taps, bands and the adjoint's workspace are
+    made on the first eager call per device and extent; later calls -- a capture among them -- hold launches only."""
+
+    MODES = {"replicate": 1, "reflect": 2, "valid": 3}
+
+    def __init__(self, kernel2d, mode):
+        if mode not in self.MODES:
+            raise ValueError(f"PaddedBlurOp: padding must be one of {tuple(self.MODES)}, got {mode!r}")
+        k = kernel2d.detach().to("cpu", torch.float64).reshape(kernel2d.shape[-2], kernel2d.shape[-1]).numpy()
+        self.mode, self.shape = mode, k.shape
+        self.pad = tuple(_bands.blur_axis_offsets(K)[1] for K in k.shape)
+        total = k.sum()
+        tv, th = k.sum(1), k.sum(0)
+        sep = np.outer(tv, th) / total if total != 0 else None
+        self.separable = sep is not None and np.abs(sep - k).max() <= 1e-12 * np.abs(k).max()
+        grow = 2 if mode == "valid" else 0
+        if self.separable:
+            tv = tv / total
+            self._sep = SeparableResampleOp(lambda n: _bands.blur_axis_matrix(n, tv, mode),
+                                            inverse_length=lambda n: n + grow * self.pad[0],
+                                            matrix_fn_w=lambda n: _bands.blur_axis_matrix(n, th, mode),
+                                            inverse_length_w=lambda n: n + grow * self.pad[1])
+        else:
+            self._host = k
+        self._dev = {}         # device -> taps
+        # (device, planes, H, W) -> the adjoint's Z canvas. Never evicted, like the bands: one padded image per distinct
+        # extent, and a run sees a handful of extents. One stream at a time may use an operator's adjoint.
+        self._work = {}
+
+    def check_extent(self, H, W):
+        """The image extents this boundary takes, refused by name before anything is built or launched."""
+        for n, K, p in zip((H, W), self.shape, self.pad):
+            if self.mode == "reflect" and p > n - 1:
+                raise ValueError(f"Blur: padding='reflect' pads by {p} for a kernel of {K} taps, which an extent of {n} "
+                                 f"cannot mirror (image {H}x{W}, kernel {self.shape[0]}x{self.shape[1]})")
+            if self.mode == "valid" and n <= 2 * p:
+                raise ValueError(f"Blur: padding='valid' needs an extent above {2 * p} for a kernel of {K} taps, got {n} "
+                                 f"(image {H}x{W}, kernel {self.shape[0]}x{self.shape[1]})")
+
+    def run(self, x, transpose, out_hw=None):
+        planes, h, w = _as_planes(x)
+        grow = 2 if self.mode == "valid" else 0
+        # (H, W): the image's extents; the measurement-sized side is smaller by 2p in `valid`
+        H, W = (h + grow * self.pad[0], w + grow * self.pad[1]) if transpose else (h, w)
+        if transpose and out_hw is not None and tuple(out_hw) != (H, W):
+            raise ValueError(f"Blur: the adjoint of a {out_hw[0]}x{out_hw[1]} image takes "
+                             f"{out_hw[0] - grow * self.pad[0]}x{out_hw[1] - grow * self.pad[1]}, got {h}x{w}")
+        self.check_extent(H, W)
+        if self.separable:
+            return self._sep.run(x, transpose, (H, W))
+        if x.device not in self._dev:
+            self._dev[x.device] = torch.tensor(self._host, dtype=torch.float32, device=x.device).contiguous()
+        k = self._dev[x.device]
+        kv, kh = self.shape
+        mode = self.MODES[self.mode]
+        ho, wo = (H, W) if transpose else (H - grow * self.pad[0], W - grow * self.pad[1])
+        y = torch.empty(x.shape[:-2] + (ho, wo), dtype=x.dtype, device=x.device)
+        work = None
+        floats = N.lib().sei_blur_dense_pad_work_floats(planes, H, W, kv, kh, mode, int(transpose))
+        if floats:
+            key = (x.device, planes, H, W)
+            if key not in self._work:
+                self._work[key] = torch.empty(floats, dtype=torch.float32, device=x.device)
+            work = self._work[key]
+        N.call("sei_blur_dense_pad", x.data_ptr(), y.data_ptr(), k.data_ptr(), kv, kh, planes, H, W, mode,
+               int(transpose), N.ptr(work))
+        return y
+
+
 # (n, None | inverse, eps, device) -> float32 first column; shared by every CirculantFilterOp. Never evicted: n floats
 # per distinct image extent, and a run sees a handful of extents.
 _CIRCULANT_COLUMNS = {}
@@ -112,17 +185,22 @@ class CirculantFilterOp:
 
 class SeparableResampleOp:
     """y = Wv x Wh^T with Wv, Wh built per input size by `matrix_fn(n_in) -> dense (n_out, n_in)`.
-    transpose=True applies Wv^T . Wh (the exact adjoint), taking the *output*-sized image."""
+    transpose=True applies Wv^T . Wh (the exact adjoint), taking the *output*-sized image. `matrix_fn_w` (with
+    `inverse_length_w`) gives the horizontal axis a matrix of its own (PaddedBlurOp: the two tap vectors of a rank-1 kernel)."""
 
-    def __init__(self, matrix_fn, inverse_length=None):
+    def __init__(self, matrix_fn, inverse_length=None, matrix_fn_w=None, inverse_length_w=None):
         self.matrix_fn = matrix_fn
         self.inverse_length = inverse_length   # n_out -> n_in, needed to transpose without a forward
+        # the horizontal axis' own matrix (and inverse length) where it differs from the vertical one
+        self.matrix_fn_w = matrix_fn_w
+        self.inverse_length_w = inverse_length_w if matrix_fn_w is not None else inverse_length
         self._cache = {}
 
-    def _axis(self, n_in, device, transpose):
-        key = (n_in, device, transpose)
+    def _axis(self, n_in, device, transpose, horizontal=False):
+        horizontal = horizontal and self.matrix_fn_w is not None
+        key = (n_in, device, transpose) + ((True,) if horizontal else ())
         if key not in self._cache:
-            dense = self.matrix_fn(n_in)
+            dense = (self.matrix_fn_w if horizontal else self.matrix_fn)(n_in)
             if transpose:
                 dense = dense.T
             w, lo, nb, step = _bands.to_band(np.ascontiguousarray(dense))
@@ -136,13 +214,13 @@ class SeparableResampleOp:
             if out_hw is not None:
                 hi, wi = out_hw
             elif self.inverse_length is not None:
-                hi, wi = self.inverse_length(H), self.inverse_length(W)
+                hi, wi = self.inverse_length(H), self.inverse_length_w(W)
             else:
                 raise RuntimeError("this resampling operator cannot be transposed without its input size")
         else:
             hi, wi = H, W
         wv, lov, nbv, sv, ho, need_h = self._axis(hi, x.device, transpose)
-        wh, loh, nbh, sh, wo, need_w = self._axis(wi, x.device, transpose)
+        wh, loh, nbh, sh, wo, need_w = self._axis(wi, x.device, transpose, horizontal=True)
         if (need_h, need_w) != (H, W):
             raise ValueError(f"resampling: image is {H}x{W} but the operator expects {need_h}x{need_w}")
         y = torch.empty(x.shape[:-2] + (ho, wo), dtype=x.dtype, device=x.device)

@@ -37,3 +37,6 @@ class DefaultArgParser(ArgumentParser):
         flag("--SingleImageDataset__duplicates_count", type=int, default=800)
         flag("--data_parallel_devices", type=str, default=None)
         flag("--physics_v2", default=True, **onoff)
+        # the boundary of the deblurring operator; anything but circular selects the legacy Blur ('valid' stays a
+        # constructor argument: the losses and test.py need A(x) at the image's size)
+        flag("--blur_padding", type=str, default="circular", choices=("circular", "replicate", "reflect"))

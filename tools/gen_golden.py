@@ -9,7 +9,7 @@ arithmetic is exercised by the goldens below except `adjoint_function`, which is
 `torch.autograd.functional.vjp` (flagged "vjp" in the fixture names).
 
 What is written is DATA ONLY: seeded inputs and the outputs the reference produced for them
-(G12 noise2inverse; G13 the in-tree R2R / EI loss; G14 CropPair on batches; G15 the loss layer end to end; G16 CTLikeFilter; G17 WeightsDistanceLoss + SGD). The reference cannot travel to the GPU box; these files can.
+(G12 noise2inverse; G13 the in-tree R2R / EI loss; G14 CropPair on batches; G15 the loss layer end to end; G16 CTLikeFilter; G17 WeightsDistanceLoss + SGD; G19 the legacy Blur's four paddings). The reference cannot travel to the GPU box; these files can.
 
     python tools/gen_golden.py            # writes tests/golden/*.npz + manifest json
 """
@@ -534,6 +534,39 @@ def gen_weights_distance():
     _save("g17_weights_distance", **arrs)
 
 
+G19_KERNELS = {"rand5x5": (5, 5), "rand4x6": (4, 6), "rand1x7": (1, 7), "rand3x1": (3, 1), "Gaussian_R1": None, "Box_R2": None}
+G19_PADDINGS = ("valid", "circular", "replicate", "reflect")
+
+
+def gen_blur_paddings():
+    """G19: the legacy Blur's `conv` / `conv_transpose` (src/physics/blur/__init__.py:34-161, loaded by path under the
+    deepinv shell: `LinearPhysics` and `adjoint_function` are only names there), float32 as the reference runs them, on
+    x (2, 3, 17, 21). Kernels: random positive ones summing to 1 (non-separable where both extents exceed 1) and two of
+    the reference's table. Stored: `k.<kernel>` (float64; the reference is handed its float32 rounding), `x`, and per kernel
+    and padding `<kernel>.<padding>.y` = conv(x), `.g` (a random cotangent of y's shape) and `.adj` = conv_transpose(g)."""
+    os.makedirs(OUT, exist_ok=True)
+    _install_deepinv_shell()
+    blur = _load_by_path("ref_blur", os.path.join(REF_SRC, "physics", "blur", "__init__.py"))
+    kernels = _load_by_path("ref_kernels", os.path.join(REF_SRC, "physics", "kernels.py"))
+    x = _rand((2, 3, 17, 21), 190)
+    arrs = {"x": _np(x)}
+    for n, (name, shape) in enumerate(G19_KERNELS.items()):
+        if shape is None:
+            k = kernels.get_kernel(name).double()        # the table's float64 values: rank one, which float32 is not
+        else:
+            k = _rand(shape, 191 + n)
+            k = (k / k.sum()).double()
+        arrs[f"k.{name}"] = _np(k)
+        f = k.float()[None, None]
+        for m, padding in enumerate(G19_PADDINGS):
+            y = blur.conv(x, f, padding)
+            g = _rand(tuple(y.shape), 200 + 4 * n + m)
+            adj = blur.conv_transpose(g, f, padding)
+            assert adj.shape == x.shape and y.dtype == adj.dtype == torch.float32
+            arrs[f"{name}.{padding}.y"], arrs[f"{name}.{padding}.g"], arrs[f"{name}.{padding}.adj"] = _np(y), _np(g), _np(adj)
+    _save("g19_blur_paddings", **arrs)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     _install_deepinv_shell()
@@ -911,6 +944,8 @@ if __name__ == "__main__":
         gen_ct_like_filter()
     elif sys.argv[1:] == ["--only", "g17"]:
         gen_weights_distance()
+    elif sys.argv[1:] == ["--only", "g19"]:
+        gen_blur_paddings()
     else:
         main()
         gen_noise2inverse()
@@ -919,3 +954,4 @@ if __name__ == "__main__":
         gen_loss_glue()
         gen_ct_like_filter()
         gen_weights_distance()
+        gen_blur_paddings()
