@@ -846,11 +846,16 @@ int sei_gemm_bf16nt_dw2_adam(const uint16_t *A1, const uint16_t *A2, int lda, co
                              int ldb, float *param, float *exp_avg, float *exp_avg_sq, uint16_t *param_bf16,
                              const float *hyper, int M, int N, int K1, int K2, void *stream);
 /* The same with the caller's schedule choice (tests of both kernels, tools/): tile 0 = the dispatcher's choice, 1 = the
- * 128 x 128 loop (gemm_bf16nt_kernel<..., ADAM>), 30 / 33 = the quadrant schedule's 256 x 256 / 256 x 128 tiles with the
- * same epilogue (gemm_bf16pq_kernel<..., ADAM>); a choice the operands do not allow falls back to the loop. */
+ * 128 x 128 loop (gemm_bf16nt_kernel<..., ADAM>), 16 = the same loop's 128 x 256 tile on 32-row stages (M % 128 == 0 and
+ * N % 256 == 0; every result bit-identical to tile 1: the same MFMA steps in the same order), 30 / 33 = the quadrant
+ * schedule's 256 x 256 / 256 x 128 tiles with the same epilogue (gemm_bf16pq_kernel<..., ADAM>); a choice the operands do
+ * not allow falls back to the 128 x 128 loop.
+ * sei_gemm_bf16nt_dw2_adam_plan: the schedule such a call would take, coded as sei_gemm_bf16nt_plan's and likewise host
+ * arithmetic only; 0 = arguments the entry point would refuse. */
 int sei_gemm_bf16nt_dw2_adam_ex(const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1, const uint16_t *B2,
                                 int ldb, float *param, float *exp_avg, float *exp_avg_sq, uint16_t *param_bf16,
                                 const float *hyper, int M, int N, int K1, int K2, int tile, void *stream);
+size_t sei_gemm_bf16nt_dw2_adam_plan(int M, int N, int K1, int K2, int tile);
 int sei_adam_scalars(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float *out6_host,
                      void *stream);
 /* the same values written to a DEVICE array by a launch on `stream` (what a training loop calls before every replay of

@@ -231,6 +231,7 @@ SIZE_QUERIES = {
     "sei_rowgemm_ln_bf16_eligible": [_L, _I, _I],
     "sei_gemm_bf16nt_plan": [_I, _I, _I, _I, _I, _I, _I, _I],
     "sei_gemm_bf16nt_plan_ws": [_I, _I, _I, _I, _I, _I, _I, _I, _Z],
+    "sei_gemm_bf16nt_dw2_adam_plan": [_I, _I, _I, _I, _I],
     "sei_conv3x3_bwd_weight_parts_count": [_I, _I, _I, _I, _I, _I, _I],
     "sei_sepmap2_small_eligible": [_I, _I, _I, _I, _I, _I],
     "sei_cast_bf16_colsum_parts_count": [_I, _I],
@@ -286,6 +287,15 @@ def gemm_plan(a_rmajor, b_rmajor, out_f32, out_bf16, M, Nn, K, epilogue, ws_byte
         raise NativeLibraryError("sei_gemm_bf16nt_plan: arguments sei_gemm_bf16nt would refuse")
     plan = {1: "nt", 2: "pq"}[code >> 48], (code >> 32) & 0xFFFF, (code >> 16) & 0xFFFF, code & 0x7FFF
     return plan + (bool(code & 0x8000),) if ws_bytes else plan
+
+
+def adam_gemm_plan(M, Nn, K1, K2, tile=0):
+    """(family, tile rows, tile columns, K splits) of the launch sei_gemm_bf16nt_dw2_adam_ex would make with this tile code
+    (sei_gemm_bf16nt_dw2_adam_plan: nothing is launched). Raises on shapes the entry point refuses."""
+    code = lib().sei_gemm_bf16nt_dw2_adam_plan(M, Nn, K1, K2, tile)
+    if code == 0:
+        raise NativeLibraryError("sei_gemm_bf16nt_dw2_adam_plan: arguments sei_gemm_bf16nt_dw2_adam_ex would refuse")
+    return {1: "nt", 2: "pq"}[code >> 48], (code >> 32) & 0xFFFF, (code >> 16) & 0xFFFF, code & 0x7FFF
 
 
 def stream():

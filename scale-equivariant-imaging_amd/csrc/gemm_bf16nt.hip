@@ -17,7 +17,8 @@
 //     Because the DMA destination is lane-linear, each swizzle is applied to the per-lane SOURCE address and
 //     again on the fragment read; SQ_LDS_BANK_CONFLICT = 0 on every variant.
 //   * double-buffered LDS, one barrier per k-tile (NSTAGE = 2); NSTAGE > 2 = ring with counted vmcnt and raw
-//     barriers (tuning variants: measured no better than two co-resident 2-stage workgroups).
+//     barriers (tuning variants: measured no better than two co-resident 2-stage workgroups -- and the 128x256 tile of the
+//     weight gradients with the Adam epilogue, whose three stages of 32 k-rows keep two workgroups on a CU: stage_rows).
 //   * tile order: each XCD walks a contiguous range of a band-major order (see the kernel prologue).
 //   * narrow outputs split K over workgroups (zero-fill kernel + float atomics), split chosen by rounds.
 //   * gemm_bf16pp.h: an opt-in 256x256 ping-pong schedule on the same LDS images.
@@ -139,11 +140,12 @@ __device__ __forceinline__ void stage_piece_rmajor(const unsigned short *__restr
     const unsigned short *src = (k < k_lim && o < o_lim) ? rowp + o : g_zero_chunk;
     dma16_lane(src, lds_tile + q * 1024);
 }
+template <int ROWS = BK>                                     // the image's first ROWS k-rows (a half image: 32)
 __device__ __forceinline__ void stage_tile_rmajor(const unsigned short *__restrict__ G,
                                                   const unsigned short *__restrict__ G2, int k_seg, int ld, int o0,
                                                   int o_lim, int k0, int k_lim, char *lds_tile, int wave, int lane) {
 #pragma unroll
-    for (int q0 = 0; q0 < 16; q0 += NWAVES)
+    for (int q0 = 0; q0 < ROWS / 4; q0 += NWAVES)
         stage_piece_rmajor(G, G2, k_seg, ld, o0, o_lim, k0, k_lim, lds_tile, q0 + wave, lane);
 }
 
@@ -168,13 +170,25 @@ constexpr bool patch_fits() {
     return (NSTAGE * (32 * TM * WM + 32 * TN * WN) * ROW_BYTES) / (32 * TN * WN * 4) >= 32 * TM;
 }
 
+// k-rows per LDS stage. The 128 x 256 weight-gradient tile on the three-stage ring (the Adam epilogue's wide tile) stages
+// HALF a reduction-major image, 32 k-rows: 24 KB per stage, 72 KB per workgroup, two workgroups per CU. swz_rmajor is a
+// function of the row alone, so the first 32 rows of an image are laid out as they are in a whole one.
+template <int TN, bool ARM, bool BRM, int NSTAGE>
+constexpr int stage_rows() { return (ARM && BRM && TN == 2 && NSTAGE == 3) ? 32 : BK; }
+
 template <int TM, int TN, int WM, int WN, bool ARM, bool BRM, int NSTAGE = 2, int ROWEPI = 0>
-__global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(NtArgs g) {
+// (second bound = waves per SIMD asked of the register allocator: the half-image tile must keep two workgroups on a CU,
+// i.e. four waves per SIMD on at most 128 registers)
+__global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : (stage_rows<TN, ARM, BRM, NSTAGE>() == 32 ? 4 : 1)))
+void gemm_bf16nt_kernel(NtArgs g) {
     static_assert(WM * WN == NWAVES, "8 waves per workgroup");
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     static_assert(!ARM || BM == 128, "a reduction-major A tile is 64 x 128");
     static_assert(!BRM || BN % 128 == 0, "a reduction-major B tile is BN/128 images of 64 k-rows x 128 columns");
-    constexpr int STAGE = (BM + BN) * ROW_BYTES;
+    constexpr int KS = stage_rows<TN, ARM, BRM, NSTAGE>();          // k-rows per stage (BK everywhere but the wide Adam tile)
+    constexpr int A_BYTES = BM * ROW_BYTES * KS / BK;               // the A tile of a stage; B follows it
+    constexpr int IMG = 256 * KS;                                   // one 128-column image of a reduction-major operand
+    constexpr int STAGE = (BM + BN) * ROW_BYTES * KS / BK;
     __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE];
 
     const int lane = threadIdx.x & 63;
@@ -289,7 +303,7 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
     // never stored). Measured on the 256x256 schedule: the per-piece 64-bit lane arithmetic and bounds selects of
     // the general path cost 20 % of the loop. Everything else (K tails, the tile that straddles k_seg) takes the
     // general path below.
-    constexpr int NPA = ARM ? 2 : (BM + 63) / 64, NPB = BN / 64;               // pieces per wave (1 KiB each)
+    constexpr int NPA = ARM ? 2 * KS / BK : (BM + 63) / 64, NPB = (BN / 64) * KS / BK;      // pieces per wave (1 KiB each)
     static_assert(BN % 64 == 0, "whole pieces per wave");
     unsigned off_a[NPA], off_b[NPB];
 #pragma unroll
@@ -307,7 +321,8 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
     for (int e = 0; e < NPB; ++e) {
         const int q = wave + NWAVES * e;
         if constexpr (BRM) {
-            const int im = q >> 4, qq = q & 15;                // 16 pieces per 128-column image
+            constexpr int PPI = KS / 4;                        // 16 pieces per 128-column image (8 per half image)
+            const int im = q / PPI, qq = q % PPI;
             const int row = 4 * qq + (lane >> 4), ch = (lane & 15) ^ swz_rmajor(row);
             off_b[e] = (unsigned)row * (unsigned)g.ldb * 2u +
                        2u * (unsigned)max(min(128 * im + 8 * ch, N - 8 - n0), 0);
@@ -317,8 +332,8 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
         }
     }
     auto rm_base = [&](const unsigned short *X1, const unsigned short *X2, int ld, int o0, int k0) -> const char * {
-        if (k0 + BK <= g.k_seg && k0 + BK <= k_end) return reinterpret_cast<const char *>(X1 + (size_t)k0 * ld + o0);
-        if (k0 >= g.k_seg && k0 + BK <= k_end) return reinterpret_cast<const char *>(X2 + (size_t)(k0 - g.k_seg) * ld + o0);
+        if (k0 + KS <= g.k_seg && k0 + KS <= k_end) return reinterpret_cast<const char *>(X1 + (size_t)k0 * ld + o0);
+        if (k0 >= g.k_seg && k0 + KS <= k_end) return reinterpret_cast<const char *>(X2 + (size_t)(k0 - g.k_seg) * ld + o0);
         return nullptr;
     };
     auto stage = [&](int k0, char *dst) {
@@ -336,7 +351,7 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
                 if (ARM || wave + NWAVES * e < BM / 8)         // wave-uniform (a 96-row tile has 12 pieces)
                     dma16_base(ab, off_a[e], dst + (wave + NWAVES * e) * 1024);
         } else {
-            if constexpr (ARM) stage_tile_rmajor(g.A, g.A2, g.k_seg, g.lda, m0, M, k0, k_end, dst, wave, lane);
+            if constexpr (ARM) stage_tile_rmajor<KS>(g.A, g.A2, g.k_seg, g.lda, m0, M, k0, k_end, dst, wave, lane);
             else stage_tile<BM>(g.A, g.lda, m0, M, k0, k_end, dst, wave, lane);
         }
         if constexpr (BRM) bb = rm_base(Bp, B2p, g.ldb, n0, k0);
@@ -344,23 +359,23 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
         if (bb) {
 #pragma unroll
             for (int e = 0; e < NPB; ++e)
-                dma16_base(bb, off_b[e], dst + BM * ROW_BYTES + (wave + NWAVES * e) * 1024);
+                dma16_base(bb, off_b[e], dst + A_BYTES + (wave + NWAVES * e) * 1024);
         } else if constexpr (BRM) {
 #pragma unroll
             for (int im = 0; im < BN / 128; ++im)           // 16 KB image per 128 columns
-                stage_tile_rmajor(Bp, B2p, g.k_seg, g.ldb, n0 + 128 * im, N, k0, k_end,
-                                  dst + BM * ROW_BYTES + im * 16384, wave, lane);
+                stage_tile_rmajor<KS>(Bp, B2p, g.k_seg, g.ldb, n0 + 128 * im, N, k0, k_end,
+                                      dst + A_BYTES + im * IMG, wave, lane);
         } else {
-            stage_tile<BN>(Bp, g.ldb, n0, N, k0, k_end, dst + BM * ROW_BYTES, wave, lane);
+            stage_tile<BN>(Bp, g.ldb, n0, N, k0, k_end, dst + A_BYTES, wave, lane);
         }
     };
     const int sw = (li >> 1) & 7;                              // swizzle key of this lane's rows
     const int a_off = (wm * 32 * TM + li) * ROW_BYTES;
-    const int b_off = BM * ROW_BYTES + (wn * 32 * TN + li) * ROW_BYTES;
+    const int b_off = A_BYTES + (wn * 32 * TN + li) * ROW_BYTES;
 
     auto compute = [&](const char *now) {
 #pragma unroll
-        for (int s = 0; s < BK / 16; ++s) {
+        for (int s = 0; s < KS / 16; ++s) {
             const int pc = ((2 * s + lh) ^ sw) * 16;
             bf16x8 a[TM], b[TN];
 #pragma unroll
@@ -372,7 +387,7 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
             for (int j = 0; j < TN; ++j) {
                 if constexpr (BRM) {
                     const int c0 = wn * 32 * TN + 32 * j;
-                    b[j] = frag_rmajor(now + BM * ROW_BYTES + (c0 >> 7) * 16384, s, lane, c0 & 127);
+                    b[j] = frag_rmajor(now + A_BYTES + (c0 >> 7) * IMG, s, lane, c0 & 127);
                 }
                 else b[j] = *reinterpret_cast<const bf16x8 *>(now + b_off + j * 32 * ROW_BYTES + pc);
             }
@@ -411,13 +426,13 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
     } else {
         // Ring of NSTAGE slots, NSTAGE-1 tiles of LDS-DMA in flight (cdna_hip_programming.md T3+T4): counted
         // vmcnt (never 0 in steady state) and a raw s_barrier, so the DMA queue never drains at a barrier.
-        // Per wave and tile the DMA count is uniform: PER = (BM + BN) / 64 instructions.
-        constexpr int PER = (BM + BN) / 64;
+        // Per wave and tile the DMA count is uniform: PER = (BM + BN) / 64 instructions (half of them for a half image).
+        constexpr int PER = (BM + BN) / 64 * KS / BK;
         static_assert((BM + BN) % 64 == 0, "uniform DMA count per wave");
-        const int nt = (k_end - k_begin + BK - 1) / BK;
+        const int nt = (k_end - k_begin + KS - 1) / KS;
 #pragma unroll
         for (int t = 0; t < NSTAGE - 1; ++t)
-            if (t < nt) stage(k_begin + t * BK, smem + t * STAGE);
+            if (t < nt) stage(k_begin + t * KS, smem + t * STAGE);
         int slot = 0;
         for (int t = 0; t < nt; ++t) {
             // tile t must have landed: everything issued after it may still be in flight
@@ -428,7 +443,7 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
             if (tn < nt) {
                 int ns = slot + NSTAGE - 1;
                 if (ns >= NSTAGE) ns -= NSTAGE;
-                stage(k_begin + tn * BK, smem + ns * STAGE);
+                stage(k_begin + tn * KS, smem + ns * STAGE);
             }
             compute(smem + slot * STAGE);
             if (++slot == NSTAGE) slot = 0;
@@ -470,14 +485,24 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
         return;
     }
     if constexpr (ROWEPI == 1) {
-        static_assert(TM == 2 && TN == 1 && WM == 2 && WN == 4, "the row patch below is laid out for the 128 x 128 tile");
+        static_assert(TM == 2 && (TN == 1 || TN == 2) && WM == 2 && WN == 4, "the row patch below is laid out for 128-row tiles");
+        static_assert(64 * BN * 4 <= NSTAGE * STAGE, "half a tile of float32 fits the operand stages");
+        constexpr int QSH = TN == 1 ? 5 : 6;                         // log2 of the quads in a patch row
         const float beta1 = g.adam_h[0], beta2 = g.adam_h[1], eps = g.adam_h[2], wd = g.adam_h[3];
         const float step_size = g.adam_h[4], inv_bc2_sqrt = g.adam_h[5];
-        float *patch = reinterpret_cast<float *>(smem);              // [64][128]
+        float *patch = reinterpret_cast<float *>(smem);              // [64][BN]
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             __builtin_amdgcn_s_barrier();                            // operands (h = 0) / the previous half are done with
-            if (wm == h) {
+            if constexpr (TN == 2) {
+                // the wide tile: every wave hands over its 32-row block h (patch rows 32 wm ..: tile rows 64 wm + 32 h ..),
+                // so that no wave carries more than half its 64 accumulator registers through the streaming below
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        patch[(32 * wm + 4 * lh + (r & 3) + 8 * (r >> 2)) * BN + 32 * TN * wn + 32 * j + li] = acc[h][j][r];
+            } else if (wm == h) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -486,17 +511,17 @@ __global__ __launch_bounds__(NT, (NSTAGE == 1 ? 3 : 1)) void gemm_bf16nt_kernel(
             }
             __syncthreads();
 #pragma unroll 1
-          for (int kk = 0; kk < 4; kk += 2) {                        // two quads at a time: registers for 3 workgroups / CU
+          for (int kk = 0; kk < 64 * BN / (4 * NT); kk += 2) {                        // two quads at a time: registers for 3 workgroups / CU
             float4 gq[2], pq[2], mq[2], vq[2];
             size_t off[2];
             bool ok[2];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {                            // 6 independent 16-byte loads per lane in flight
-                const int idx = threadIdx.x + NT * (kk + k), r = idx >> 5, c4 = idx & 31;
-                const int row = m0 + 64 * h + r, col = n0 + 4 * c4;
+                const int idx = threadIdx.x + NT * (kk + k), r = idx >> QSH, c4 = idx & (BN / 4 - 1);
+                const int row = m0 + (TN == 2 ? 64 * (r >> 5) + 32 * h + (r & 31) : 64 * h + r), col = n0 + 4 * c4;
                 ok[k] = row < M && col < N;                          // N % 8 == 0: a quad is all in or all out
                 off[k] = ok[k] ? (size_t)row * N + col : 0;
-                gq[k] = *reinterpret_cast<const float4 *>(patch + r * 128 + 4 * c4);
+                gq[k] = *reinterpret_cast<const float4 *>(patch + r * BN + 4 * c4);
                 // streamed once per step: non-temporal, so that they do not push the GEMM operands out of L2 / MALL
                 pq[k] = nt_load4(g.adam_p + off[k]);
                 mq[k] = nt_load4(g.adam_m + off[k]);
@@ -712,7 +737,7 @@ int launch_nt(NtArgs &g, hipStream_t s) {
     const size_t nbatch = g.batch > 1 ? (size_t)g.batch : 1;
     SEI_REQUIRE(tiles * nbatch < ((size_t)1 << 27));
     {
-        constexpr size_t STAGE_BYTES = NSTAGE * (size_t)(BM + BN) * ROW_BYTES;
+        constexpr size_t STAGE_BYTES = NSTAGE * (size_t)(BM + BN) * ROW_BYTES * stage_rows<TN, ARM, BRM, NSTAGE>() / BK;
         const double conc = 32.0 * (STAGE_BYTES <= 40 * 1024 ? 3 : (STAGE_BYTES <= 80 * 1024 ? 2 : 1));   // tiles in flight per XCD
         int band = g.force_band > 0 ? g.force_band : (int)(sqrt(conc * BM / BN) + 0.5);   // square patch in elements
         if (band < 1) band = 1;
@@ -727,7 +752,7 @@ int launch_nt(NtArgs &g, hipStream_t s) {
     if ((ROWEPI == 0 || ROWEPI == 3) && splittable && g.D32 && !g.D16 && g.K >= 8 * BK) {
         // Wave-quantisation-aware split: a launch takes ceil(tiles*sk / slots) rounds of workgroups, each
         // round costing (k-tiles per split + a fixed prologue/epilogue/atomics overhead); pick the cheapest sk.
-        constexpr size_t STAGE_BYTES = NSTAGE * (size_t)(BM + BN) * ROW_BYTES;
+        constexpr size_t STAGE_BYTES = NSTAGE * (size_t)(BM + BN) * ROW_BYTES * stage_rows<TN, ARM, BRM, NSTAGE>() / BK;
         const size_t slots = 256 * (STAGE_BYTES <= 40 * 1024 ? 3 : (STAGE_BYTES <= 80 * 1024 ? 2 : 1));   // resident workgroups
         const size_t ktiles = sei_ceil_div(g.K, BK);
         // up to 256 splits: a one-tile weight gradient of the shallow levels (128 x 32 outputs, K = 221,184 =
@@ -908,16 +933,43 @@ int pq_choose_rr(const NtArgs &g) {
     return 84;
 }
 
-// The weight-gradient GEMMs whose epilogue applies the Adam step stay on the 128 x 128 loop: two workgroups per CU overlap
+// The weight-gradient GEMMs whose epilogue applies the Adam step stay on the 128-row loop: two workgroups per CU overlap
 // one's 26-byte-per-element epilogue with the other's main loop (tools/exp_dw_adam_pq.py: 8192 x 32768 x 864 1288 us =
 // 5.5 TB/s against 1537 us on 256 x 256 quadrant tiles, 2048 x 8192 x 3456 178 against 182 us). The quadrant kernel's Adam
 // epilogue stays reachable through sei_gemm_bf16nt_dw2_adam_ex (tile 30 / 33) and is held to the loop's results by a test.
 // (The two co-resident workgroups run in phase -- both in the main loop, then both in the epilogue. Starting every CU's
 // second workgroup late by 7 - 40 us, so that one's epilogue falls under the other's main loop, only ADDS the delay:
 // tools/exp_adam_stagger.py, 2048 x 8192 x 3456 184 -> 188 ... 210 us, 8192 x 32768 x 864 1409 -> 1412 ... 1434. The main loop
-// of a 128 x 128 tile moves 1.77 MB of operands through the CU's global -> LDS path against the epilogue's 0.43 MB: both
-// phases are bound by that same path, so there is nothing to hide one under the other.)
+// of a 128 x 128 tile moves 1.77 MB of operands through the CU's global -> LDS path against the epilogue's 0.43 MB. That
+// path is what bounds the main loop -- the 128 x 256 tile below moves 3/4 of the bytes and its loop runs 1.3 - 1.5 times
+// faster -- but NOT the epilogue: that one is HBM's, and cut out of the launch it takes as long on either tile.)
 bool pq_adam_auto(const NtArgs &) { return false; }
+
+// The 128 x 256 tile of the same loop (launch_nt<2, 2, 2, 4, true, true, 3, 1>): per output element a workgroup stages
+// (BM + BN) / (BM BN) operand elements, 3/4 of the 128 x 128 tile's, on 32-row stages that still fit two workgroups on a CU
+// (stage_rows), with the same MFMA steps in the same order: every result bit-identical. Measured per launch, alternating
+// with the 128 x 128 loop on one MI355X (profiles/r07_adam_wide_tile.md; us, narrow -> wide):
+//   8192 x 32768 x 864  1313 -> 1246     32768 x 8192 x 864  1299 -> 1244     (the bottleneck pair, 16 rounds of workgroups)
+//   2048 x 8192 x 3456   181 ->  169      8192 x 2048 x 3456  175 ->  168     (level 3, one round)
+//   8192 x 2048 x 864     97 ->  103     (one round of a short reduction: all prologue and epilogue -- stays narrow)
+// The main loop alone runs 1.3 - 1.5 times faster on the wide tile (level 3: ~133 -> ~98 us, the pair: 500 -> 325 us with
+// the epilogue cut out); the launches gain far less because the epilogue's 26 bytes per element set their length (the pair:
+// the epilogue alone, every workgroup streaming at once, takes 1.1 - 1.4 ms; on the step's own buckets the pair gains only
+// 10 - 20 us per launch) and because the single round of level 3 runs all its main loops and then all its epilogues: loop
+// ~98 us + epilogue ~88 us = the launch. Whole tiles only, enough of them to
+// fill the 2 x 256 workgroup slots of the chip in every round, and a long reduction or many rounds.
+bool adam_wide_fits(const NtArgs &g) { return g.M % 128 == 0 && g.N % 256 == 0; }
+bool adam_wide_auto(const NtArgs &g) {
+    if (!adam_wide_fits(g)) return false;
+    const size_t tiles = (size_t)(g.M / 128) * (size_t)(g.N / 256);
+    if (tiles < 512 || (double)tiles / (double)(sei_ceil_div(tiles, 512) * 512) < 0.8) return false;
+    return g.K >= 2048 || tiles >= 4096;
+}
+// Tile order of the wide tile: bands of 8 tile columns (the XCD's 64 tiles in flight = 8 x 8 tiles, 1024 rows x 2048 columns,
+// 8 KB of every parameter row at a time) instead of launch_nt's square patch in elements (6). Measured, us, bands of
+// 6 / 8 / 12 / 16 / 24: 8192 x 32768: 1244 / 1247 / 1259 / 1285 / 1363; 32768 x 8192: 1261 / 1244 / 1293 / 1318 / 1399;
+// 2048 x 8192 x 3456: 178 / 169 / 168 / 169 / 172; 8192 x 2048 x 3456: 180 / 169 / 166 / 166 / 168.
+constexpr int ADAM_WIDE_BAND = 8;
 
 extern "C" int sei_colsum_bf16(const uint16_t *X, float *out, size_t M, int N, void *stream);     // bf16_support.hip
 
@@ -1250,6 +1302,25 @@ extern "C" int sei_gemm_bf16nt_dw2_ex(const uint16_t *A1, const uint16_t *A2, in
     return launch_nt<2, 1, 2, 4, true, true>(g, (hipStream_t)stream);
 }
 
+// The schedule of a weight-gradient GEMM with the Adam epilogue: launches it, or with g.plan only reports it.
+static int dw2_adam_dispatch(NtArgs &g, int tile, hipStream_t s) {
+    SEI_REQUIRE(tile == 0 || tile == 1 || tile == 16 || tile == 30 || tile == 33);
+    // tile 30 / 33: the quadrant schedule's 256 x 256 / 256 x 128 tiles with the Adam epilogue (round 5): half the operand
+    // bytes per output element of the 128 x 128 loop
+    if ((tile == 30 || tile == 33 || (tile == 0 && pq_adam_auto(g))) && pq_eligible(g, true)) {
+        if (tile == 33) return launch_pq<8, 2, true, true, 0, 2, true>(g, s);
+        return launch_pq<8, 4, true, true, 0, 2, true>(g, s);
+    }
+    // tile 16: the loop's 128 x 256 tile on 32-row stages (adam_wide_auto)
+    if ((tile == 16 && adam_wide_fits(g)) || (tile == 0 && adam_wide_auto(g))) {
+        g.force_band = ADAM_WIDE_BAND;
+        return launch_nt<2, 2, 2, 4, true, true, 3, 1>(g, s);
+    }
+    // (the double-buffered loop: with the Adam epilogue's 112 registers only two workgroups fit a CU, which is what
+    // the one-stage loop was meant to beat with three; measured at K = 864: 1416-1421 us against 1426-1459)
+    return launch_nt<2, 1, 2, 4, true, true, 2, 1>(g, s);
+}
+
 extern "C" int sei_gemm_bf16nt_dw2_adam_ex(const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1,
                                            const uint16_t *B2, int ldb, float *param, float *exp_avg, float *exp_avg_sq,
                                            uint16_t *param_bf16, const float *hyper, int M, int N, int K1, int K2,
@@ -1260,16 +1331,21 @@ extern "C" int sei_gemm_bf16nt_dw2_adam_ex(const uint16_t *A1, const uint16_t *A
                 ((uintptr_t)param_bf16 & 7) == 0);              // the epilogue moves whole quads
     g.D32 = param;
     g.adam_p = param; g.adam_m = exp_avg; g.adam_v = exp_avg_sq; g.adam_p16 = param_bf16; g.adam_h = hyper;
-    SEI_REQUIRE(tile == 0 || tile == 1 || tile == 30 || tile == 33);
-    // tile 30 / 33: the quadrant schedule's 256 x 256 / 256 x 128 tiles with the Adam epilogue (round 5): half the operand
-    // bytes per output element of the 128 x 128 loop
-    if ((tile == 30 || tile == 33 || (tile == 0 && pq_adam_auto(g))) && pq_eligible(g, true)) {
-        if (tile == 33) return launch_pq<8, 2, true, true, 0, 2, true>(g, (hipStream_t)stream);
-        return launch_pq<8, 4, true, true, 0, 2, true>(g, (hipStream_t)stream);
-    }
-    // (the double-buffered loop: with the Adam epilogue's 112 registers only two workgroups fit a CU, which is what
-    // the one-stage loop was meant to beat with three; measured at K = 864: 1416-1421 us against 1426-1459)
-    return launch_nt<2, 1, 2, 4, true, true, 2, 1>(g, (hipStream_t)stream);
+    return dw2_adam_dispatch(g, tile, (hipStream_t)stream);
+}
+
+// The schedule sei_gemm_bf16nt_dw2_adam_ex would take (coded as sei_gemm_bf16nt_plan's), launching nothing; operands taken
+// as densely packed and aligned. 0 = arguments the entry point would refuse.
+extern "C" size_t sei_gemm_bf16nt_dw2_adam_plan(int M, int N, int K1, int K2, int tile) {
+    const uint16_t *fake16 = reinterpret_cast<const uint16_t *>(uintptr_t(1) << 20);      // never dereferenced
+    float *fake32 = reinterpret_cast<float *>(uintptr_t(1) << 20);
+    unsigned long long plan = 0;
+    NtArgs g;
+    if (nt_fill_dw2(g, fake16, fake16, M, fake16, fake16, N, M, N, K1, K2, 1) != SEI_OK) return 0;
+    g.D32 = fake32;
+    g.adam_p = g.adam_m = g.adam_v = fake32; g.adam_h = fake32;
+    g.plan = &plan;
+    return dw2_adam_dispatch(g, tile, nullptr) == SEI_OK ? (size_t)plan : 0;
 }
 
 extern "C" int sei_gemm_bf16nt_dw2_adam(const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1,
