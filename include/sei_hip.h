@@ -1099,6 +1099,40 @@ int sei_cg_direction(float *p, const float *r, const SeiCgState *state, size_t n
 int sei_diffpir_sample(const float *u, float *x, const float *nz, float *xin, float sa_t, float s1m_t, float sa_n,
                        float s1m_n, float zeta, float at_n, size_t n, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The DPS baseline (models/dps.py; deepinv v0.2.0's sampling.DPS restated): every step differentiates the data term
+ * through the denoiser, so the DRUNet family above gains the one launch its backward pass lacks, and the step itself runs
+ * on float32 streaming kernels with every scalar on the device.
+ *
+ *   sei_drunet_conv3x3_masked   Y16 = bf16(conv(X)) where the bf16 grid Mask (the output's shape) is above zero, else 0:
+ *                               the first half of a ResBlock's backward, Mask the taped ReLU output of its first
+ *                               convolution and Wt the transposed weights of its second. Tiles, the interior-rows rule and
+ *                               the bits-per-pb promise are sei_drunet_conv3x3's; Mask may not be Y16. (The transposed
+ *                               operators are the forward's shapes with repacked weights: a 3x3 convolution with flipped
+ *                               taps, down^T on sei_drunet_up, up^T on sei_drunet_down, tail^T on sei_drunet_head with
+ *                               sigma = 0, head^T on sei_drunet_tail; the block's second half is epilogue 1.) */
+int sei_drunet_conv3x3_masked(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W,
+                              const uint16_t *Mask, uint16_t *Y16, void *stream);
+int sei_drunet_conv3x3_masked_ex(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W,
+                                 const uint16_t *Mask, uint16_t *Y16, int pb, void *stream);
+/* The step kernels stream B images of m >= 1 floats each (B m contiguous floats; tensor pointers 16-byte aligned, the
+ * per-image scalars 4; an image's start need not be aligned). -ffp-contract=off: the float32 operations as written.
+ *   sei_dps_u         u = clamp(2 out - 1, -1, 1) / 2 + 0.5.
+ *   sei_dps_residual  r = Au - y; f[b] = 0.5 ||r_b||^2; s[b] = 1 / (2 sqrt(f[b])), 0 where f[b] is not above 0. One partial
+ *                     per workgroup in part (sei_dps_partials(B, m) floats, 0 = arguments refused) and a one-workgroup
+ *                     fold in the library's fold order: no atomics, the same bits on every run and at every batch position.
+ *   sei_dps_seed      seed = Atr where -1 <= 2 out - 1 <= 1 (the clamp's derivative, inclusive), else 0.
+ *   sei_dps_step      x0 = clamp(2 out - 1, -1, 1);  x = ((c0 x0 + st nz) + c1 x) - (ginv s[b]) gx   (in place);
+ *                     xin = x / den + 0.5 (den = 2 sqrt(alpha) of the next timestep; 2 behind the last pair, where xin is
+ *                     the result). out, gx, nz and xin must not be x. */
+size_t sei_dps_partials(int B, size_t m);
+int sei_dps_u(const float *out, float *u, int B, size_t m, void *stream);
+int sei_dps_residual(const float *Au, const float *y, float *r, float *part, float *f, float *s, int B, size_t m,
+                     void *stream);
+int sei_dps_seed(const float *Atr, const float *out, float *seed, int B, size_t m, void *stream);
+int sei_dps_step(const float *out, const float *gx, const float *nz, const float *s, float *x, float *xin, float c0, float c1,
+                 float st, float ginv, float den, int B, size_t m, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,12 @@ SIGNATURES = {
     "sei_cg_update": [_P, _P, _P, _P, _F, _P, _P, _Z, _P],
     "sei_cg_direction": [_P, _P, _P, _Z, _P],
     "sei_diffpir_sample": [_P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _Z, _P],
+    "sei_drunet_conv3x3_masked": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "sei_drunet_conv3x3_masked_ex": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
+    "sei_dps_u": [_P, _P, _I, _Z, _P],
+    "sei_dps_residual": [_P, _P, _P, _P, _P, _P, _I, _Z, _P],
+    "sei_dps_seed": [_P, _P, _P, _I, _Z, _P],
+    "sei_dps_step": [_P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _Z, _P],
 }
 
 _lib = None
@@ -238,6 +244,7 @@ SIZE_QUERIES = {
     "sei_sgd_partials": [_Z, _Z, _I],
     "sei_drunet_work_bytes": [_I, _I, _I],
     "sei_cg_partials": [_Z],
+    "sei_dps_partials": [_I, _Z],
 }
 ABI_VERSION = 12      # SEI_ABI_VERSION of include/sei_hip.h this table was written against
 

@@ -14,12 +14,16 @@
 // Every output element is one wave's k-ordered MFMA chain over its own row's inputs: no split-K, no atomics, the same
 // bits on every run and wherever the image sits in the batch. Only interior rows are written: the border of an output
 // grid stays as the caller zeroed it, guard rows are read (into results that are dropped) and never written.
+//
+// The network's vector-Jacobian product (models/drunet.py, for the DPS baseline) is the same family with transposed weights
+// and one more epilogue, DR_MASK16: Y16 = bf16(conv(X)) where a taped bf16 grid (a ResBlock's ReLU output) is above zero,
+// else 0 -- the first half of the block's backward (sei_drunet_conv3x3_masked).
 #include "sei_common.h"
 
 namespace {
 
 enum { DR_SHIFT = 0, DR_DOWN = 1 };          // where tap t of row r reads: r + its row shift / the 2x2 gather
-enum { DR_RELU16 = 0, DR_RES = 1, DR_UP = 2, DR_TAIL = 3 };
+enum { DR_RELU16 = 0, DR_RES = 1, DR_UP = 2, DR_TAIL = 3, DR_MASK16 = 4 };
 
 struct DrArgs {
     const uint16_t *X;                       // row 0 of the input grid
@@ -30,6 +34,7 @@ struct DrArgs {
     int Cin, ntaps, N, M;                    // M = rows of the grid the launch walks
     int H, W;                                // interior extents of that grid
     int Cout;                                // DR_UP: N = 4 Cout; DR_TAIL: channels of the image
+    const uint16_t *Mask;                    // DR_MASK16: row 0 of a bf16 grid of the output's shape, kept where it is > 0
 };
 
 // One wave per workgroup: PB 16-row blocks of grid rows x NB 16-channel blocks. The reduction runs in steps of 32 channels
@@ -116,6 +121,13 @@ __global__ __launch_bounds__(64) void drunet_gemm_kernel(const DrArgs a) {
                 const size_t at = (size_t)mrow[p] * a.N + n;
                 *reinterpret_cast<u32x2 *>(a.Y16 + at) =
                     u32x2{sei_pack2_bf16(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)), sei_pack2_bf16(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f))};
+            } else if (EPI == DR_MASK16) {             // the ResBlock's backward: the ReLU's derivative from its taped output
+                const size_t at = (size_t)mrow[p] * a.N + n;
+                const u32x2 m = *reinterpret_cast<const u32x2 *>(a.Mask + at);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)            // a bf16 is above zero when its bits, read as int16, are
+                    if ((int16_t)(m[e >> 1] >> (16 * (e & 1))) <= 0) v[e] = 0.f;
+                *reinterpret_cast<u32x2 *>(a.Y16 + at) = u32x2{sei_pack2_bf16(v[0], v[1]), sei_pack2_bf16(v[2], v[3])};
             } else if (EPI == DR_RES) {
                 const size_t at = (size_t)mrow[p] * a.N + n;
                 if (a.Tin) v = *reinterpret_cast<const f32x4 *>(a.Tin + at) + v;
@@ -219,6 +231,22 @@ extern "C" int sei_drunet_conv3x3_ex(const uint16_t *X, const uint16_t *Wt, int 
 extern "C" int sei_drunet_conv3x3(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W, int epilogue,
                                   const float *T_in, const float *T_skip, float *T_out, uint16_t *Y16, void *stream) {
     return sei_drunet_conv3x3_ex(X, Wt, Cin, Cout, B, H, W, epilogue, T_in, T_skip, T_out, Y16, 0, stream);
+}
+
+extern "C" int sei_drunet_conv3x3_masked_ex(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W,
+                                            const uint16_t *Mask, uint16_t *Y16, int pb, void *stream) {
+    SEI_REQUIRE(pb == 0 || dr_pb_ok(pb));
+    SEI_REQUIRE(X && Wt && Mask && Y16 && X != Y16 && Mask != Y16 && dr_al16(X) && dr_al16(Wt) && dr_al16(Mask) && dr_al16(Y16));
+    SEI_REQUIRE(dr_width(Cin) && dr_width(Cout));
+    const long long R = dr_rows(B, H, W);
+    SEI_REQUIRE(R > 0);
+    DrArgs a{X, Wt, nullptr, nullptr, nullptr, Y16, Cin, 9, Cout, (int)R, H, W, Cout, Mask};
+    return dr_launch<4, DR_SHIFT, DR_MASK16>(a, pb, (hipStream_t)stream);
+}
+
+extern "C" int sei_drunet_conv3x3_masked(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int H, int W,
+                                         const uint16_t *Mask, uint16_t *Y16, void *stream) {
+    return sei_drunet_conv3x3_masked_ex(X, Wt, Cin, Cout, B, H, W, Mask, Y16, 0, stream);
 }
 
 extern "C" int sei_drunet_down(const uint16_t *X, const uint16_t *Wt, int Cin, int Cout, int B, int Ho, int Wo, float *T_out,

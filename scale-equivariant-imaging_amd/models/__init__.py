@@ -17,8 +17,11 @@ pretrained weights with --drunet_weights, nothing is fetched; parity with deepin
 pinned truth) and "DiffPIR_DRUNet" (models/diffpir.py: deepinv's DiffPIR restated around the same DRUNet and the same
 --drunet_weights, its data step on the fused sei_cg_* conjugate-gradient kernels and its sampling step on
 sei_diffpir_sample; --diffpir_iterations, default 100; parity with deepinv unpinned, tests/diffpir_ref.py is the pinned
-truth). The other test-time baselines (BM3D, DiffPIR_DiffUNet, DPS) need a second pretrained network or a package that is
-not here; they raise a clear error instead of silently running something else. (A second pretrained network sits outside this
+truth) and "DPS" (models/dps.py: deepinv's DPS restated around the same DRUNet and the same --drunet_weights; every step
+differentiates its data term through the denoiser, on DRUNet.forward_taped / DRUNet.vjp -- the sei_drunet_* family with
+transposed weights and sei_drunet_conv3x3_masked -- and the sei_dps_* step kernels; --dps_iterations, default 1000; parity
+with deepinv unpinned, tests/dps_ref.py is the pinned truth). The other test-time baselines (BM3D, DiffPIR_DiffUNet) need a
+second pretrained network or a package that is not here; they raise a clear error instead of silently running something else. (A second pretrained network sits outside this
 factory: the AlexNet features of the LPIPS metric, metrics.LPIPS, five convolutions whose two small published weight files
 the user names to test.py.)
 """
@@ -33,11 +36,12 @@ from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
 from .diffpir import DiffPIR
 from .dip import DeepImagePrior
+from .dps import DPS
 from .drunet import DRUNet
 from .pnp import PnPModel
 from .tv import TV
 
-_OUT_OF_SCOPE = ("BM3D", "DiffPIR_DiffUNet", "DPS")
+_OUT_OF_SCOPE = ("BM3D", "DiffPIR_DiffUNet")
 
 
 class Identity(Module):
@@ -136,6 +140,17 @@ class Model(Module):
                                           "A_adjoint: it cannot run on a folder of measurements without a physics")
             self.model = DiffPIR(physics=physics, denoiser=DRUNet.from_file(weights, device),
                                  max_iter=blueprint[DiffPIR.__name__]["max_iter"])
+        elif kind == "DPS":                                   # reference src/models/dps.py: DPSBase(DRUNet, L2())
+            weights = blueprint[DPS.__name__]["drunet_weights"]
+            if weights is None:
+                raise NotImplementedError("model kind 'DPS' runs a pretrained DRUNet and nothing is fetched: name its state "
+                                          "dict (KAIR's drunet_color.pth) with --drunet_weights")
+            if not callable(getattr(physics, "A", None)) or not callable(getattr(physics, "A_adjoint", None)):
+                raise NotImplementedError("model kind 'DPS' differentiates its data term through the physics' A and "
+                                          "A_adjoint: a folder of measurements without a physics, or a physics without "
+                                          "them, stays outside what this build can run")
+            self.model = DPS(physics=physics, denoiser=DRUNet.from_file(weights, device),
+                             max_iter=blueprint[DPS.__name__]["max_iter"])
         elif kind in _OUT_OF_SCOPE:
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
                                       "hot path this build implements")
@@ -209,6 +224,8 @@ def get_model(args, physics, device):
         DiffPIR.__name__: {"drunet_weights": getattr(args, "drunet_weights", None),
                            "max_iter": 100 if getattr(args, "diffpir_iterations", None) is None
                            else args.diffpir_iterations},
+        DPS.__name__: {"drunet_weights": getattr(args, "drunet_weights", None),
+                       "max_iter": 1000 if getattr(args, "dps_iterations", None) is None else args.dps_iterations},
         TV.__name__: {"lambd": getattr(args, "tv_lambd", None), "max_iter": getattr(args, "tv_max_iter", None) or 300},
     }
     return Model(blueprint=blueprint, physics=physics, device=device,

@@ -26,3 +26,8 @@ class Downsampling(LinearPhysics):
         if self.true_adjoint:
             return apply_linear(self._down, y.contiguous(), transpose=True)
         return apply_linear(self._up, y.contiguous())
+
+    def A_transpose(self, y):
+        """The exact transpose of A whatever `true_adjoint` says: what differentiating a data term through A takes
+        (models/dps.py)."""
+        return apply_linear(self._down, y.contiguous(), transpose=True)

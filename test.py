@@ -19,11 +19,14 @@ on the sei_drunet_* kernels per image; FILE is the state dict of KAIR's drunet_c
 raises and names it) and `--model_kind DiffPIR_DRUNet --drunet_weights FILE [--diffpir_iterations N]` (models/diffpir.py:
 deepinv's DiffPIR restated around the same DRUNet, N = 100 denoiser calls per image by default and between them the data
 step's conjugate gradients on the fused sei_cg_* kernels and the sampling step on sei_diffpir_sample; its noise comes from
-torch's generator, seeded above like everything else). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
+torch's generator, seeded above like everything else) and `--model_kind DPS --drunet_weights FILE [--dps_iterations N]`
+(models/dps.py: deepinv's DPS restated around the same DRUNet; every one of its N = 1000 default steps is a denoiser forward
+and a vector-Jacobian product through it, DRUNet.forward_taped / DRUNet.vjp on the sei_drunet_* kernels, with the step itself
+on the sei_dps_* kernels: the heaviest path of this driver). `--ssim` (build-side addition) computes the luma SSIM (metrics.ssim_fn, sei_ssim_luma) for the
 `SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. `--lpips_backbone FILE --lpips_linear FILE`
 (build-side addition; both or neither) name a torchvision AlexNet state dict and the LPIPS v0.1 `alex` linear layers: the
 `LPIPS:`, `LPIPS std:` and `LIPS:` fields then carry metrics.lpips_fn's values (the sei_lpips_* kernels); without them they
-print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: the BM3D / DiffPIR_DiffUNet / DPS
+print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: the BM3D / DiffPIR_DiffUNet
 baselines (a second pretrained network or the bm3d package).
 """
 import os
@@ -69,6 +72,7 @@ def build_parser():
     flag("--lpips_linear", type=str, default=None, metavar="FILE")                       # build-side addition
     flag("--drunet_weights", type=str, default=None, metavar="FILE")                     # build-side addition
     flag("--diffpir_iterations", type=int, default=100)                                  # build-side addition
+    flag("--dps_iterations", type=int, default=1000)                                     # build-side addition
     return parser
 
 
