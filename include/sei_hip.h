@@ -44,7 +44,8 @@ extern "C" {
  *                sei_ln_fwd, sei_ln_bwd (+ sei_ln_bwd_workspace), sei_gemm_f32, sei_colsum_f32, sei_sepmap2
  *   U-Net (bf16) sei_cast_bf16, sei_ln_fwd_bf16, sei_gemm_bf16nt
  *   optimizer    sei_adam_fused, sei_sgd_fused (+ sei_sgd_partials, sei_sgd_penalty_finish)
- *   baselines    sei_tv_prox (+ sei_tv_prox_work_floats)
+ *   baselines    sei_tv_prox (+ sei_tv_prox_work_floats), sei_bm3d_match (+ sei_bm3d_ref_blocks), sei_bm3d_ht,
+ *                sei_bm3d_wiener, sei_bm3d_finish
  * INTERNAL -- everything else in this header: fused, schedule-specific (_ex, _ws, _dw2*, _plan, _eligible, _parts,
  * _count ...), SwinIR and measurement entry points that this build's own host layer (models/_ops.py, graphs.py, optim.py,
  * bench.py) calls. They are exported and documented here because that host layer sits above the C ABI, but they follow the
@@ -53,7 +54,7 @@ extern "C" {
 
 /* ABI version of this header; sei_abi_version() returns the value the library was built with. Adding an entry point
  * is backward compatible and does not change it: sei_circ_filter_sep, sei_blur_sep_circ_lds, sei_resample_sepband_lds,
- * sei_blur_dense_pad and sei_blur_dense_pad_work_floats joined version 12 that way (a binding written against an earlier 12 keeps working; one that needs a new symbol checks
+ * sei_blur_dense_pad, sei_blur_dense_pad_work_floats and the sei_bm3d_* family joined version 12 that way (a binding written against an earlier 12 keeps working; one that needs a new symbol checks
  * for it by name). */
 #define SEI_ABI_VERSION 12
 int sei_abi_version(void);
@@ -1132,6 +1133,41 @@ int sei_dps_residual(const float *Au, const float *y, float *r, float *part, flo
 int sei_dps_seed(const float *Atr, const float *out, float *seed, int B, size_t m, void *stream);
 int sei_dps_step(const float *out, const float *gx, const float *nz, const float *s, float *x, float *xin, float c0, float c1,
                  float st, float ginv, float den, int B, size_t m, void *stream);
+
+/* ---- the BM3D baseline (models/bm3d.py; csrc/bm3d_kernels.hip). Reference: src/models/bm3d_deblurring.py calls the bm3d
+ * package, which is not part of the reference tree: the algorithm is restated in models/bm3d.py and pinned by
+ * tests/bm3d_ref.py. `planes` images of H x W float32 (H, W >= 8), blocks of 8 x 8. The reference positions of an axis of
+ * extent m are 0, step, 2 step ... and m - 8 last; sei_bm3d_ref_blocks(H, W, step) is their number per plane (0 = arguments
+ * refused), row-major over (row position, column position). Groups: pos[planes][ref blocks][n_max][2] int32 (row, column of a
+ * block's first pixel) and counts[planes][ref blocks] int32, n_max one of 1, 2, 4, 8, 16, 32; window odd.
+ *   sei_bm3d_match   per reference block at (r, c): d = sum(diff^2) / 64 against every block position (r', c') of the image
+ *                    with |r' - r|, |c' - c| <= window / 2; the n_max smallest with d <= tau in the order (d, r', c'), cut to
+ *                    the largest power of two not above their number. Slots behind the count hold (r, c). dist (may be
+ *                    NULL): [planes][ref blocks][n_max] the kept distances, +inf behind the count. The same bits on every run.
+ *   sei_bm3d_ht      8 x 8 DCT-II and Haar along the group, coefficients kept where |c| > lambd sqrt(var[plane][i]), group
+ *                    weight 1 / (sum of var over the kept; 1 when none), inverse, and work[0] += w K block, work[1] += w K
+ *                    (work: 2 x planes H W floats, zeroed by the call; K = kaiser(8, 2.0) x kaiser(8, 2.0)). coef (may be
+ *                    NULL): [planes][ref blocks][n_max][64] doubles, the group's transform coefficients before the shrinkage.
+ *                    Its transforms and its keep / drop decisions are in double (lambd is a double): they agree with a
+ *                    float64 computation on the same float32 inputs except at ties of about 1e-15.
+ *   sei_bm3d_wiener  the same with the shrinkage P^2 / (P^2 + var) from the pilot's group at the same positions and the
+ *                    weight 1 / sum(W^2 var).
+ *                    Both clamp positions to [0, H-8] x [0, W-8] and counts to a power of two in [1, n_max]: no index buffer
+ *                    makes them touch memory outside the planes. agg: 0 sums a tile's blocks in LDS before the global float
+ *                    atomics, 1 adds every block row to global memory; either way the result is reproducible to rounding
+ *                    only. var: [planes][64].
+ *   sei_bm3d_finish  out = work[0] / work[1] (0 where work[1] is 0).
+ * SEI_ERR_BAD_ARG on NULL or misaligned pointers, planes < 1, H or W below 8, step < 1, an even or non-positive window, an
+ * n_max outside the list, a negative or non-finite tau / lambd, agg outside {0, 1}; SEI_ERR_TOO_LARGE when the search region
+ * or the tile's footprint does not fit 64 KiB of LDS, or the index arithmetic would overflow. */
+size_t sei_bm3d_ref_blocks(int H, int W, int step);
+int sei_bm3d_match(const float *img, int planes, int H, int W, int step, int window, float tau, int n_max, int *pos,
+                   int *counts, float *dist, void *stream);
+int sei_bm3d_ht(const float *noisy, const float *var, const int *pos, const int *counts, int planes, int H, int W, int step,
+                int n_max, int window, double lambd, int agg, float *work, double *coef, void *stream);
+int sei_bm3d_wiener(const float *noisy, const float *pilot, const float *var, const int *pos, const int *counts, int planes,
+                    int H, int W, int step, int n_max, int window, int agg, float *work, void *stream);
+int sei_bm3d_finish(const float *work, float *out, int planes, int H, int W, void *stream);
 
 #ifdef __cplusplus
 }

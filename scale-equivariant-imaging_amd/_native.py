@@ -162,6 +162,10 @@ SIGNATURES = {
     "sei_dps_residual": [_P, _P, _P, _P, _P, _P, _I, _Z, _P],
     "sei_dps_seed": [_P, _P, _P, _I, _Z, _P],
     "sei_dps_step": [_P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _Z, _P],
+    "sei_bm3d_match": [_P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P],
+    "sei_bm3d_ht": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _c.c_double, _I, _P, _P, _P],
+    "sei_bm3d_wiener": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "sei_bm3d_finish": [_P, _P, _I, _I, _I, _P],
 }
 
 _lib = None
@@ -245,6 +249,7 @@ SIZE_QUERIES = {
     "sei_drunet_work_bytes": [_I, _I, _I],
     "sei_cg_partials": [_Z],
     "sei_dps_partials": [_I, _Z],
+    "sei_bm3d_ref_blocks": [_I, _I, _I],
 }
 ABI_VERSION = 12      # SEI_ABI_VERSION of include/sei_hip.h this table was written against
 

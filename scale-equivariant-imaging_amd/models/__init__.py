@@ -20,8 +20,12 @@ sei_diffpir_sample; --diffpir_iterations, default 100; parity with deepinv unpin
 truth) and "DPS" (models/dps.py: deepinv's DPS restated around the same DRUNet and the same --drunet_weights; every step
 differentiates its data term through the denoiser, on DRUNet.forward_taped / DRUNet.vjp -- the sei_drunet_* family with
 transposed weights and sei_drunet_conv3x3_masked -- and the sei_dps_* step kernels; --dps_iterations, default 1000; parity
-with deepinv unpinned, tests/dps_ref.py is the pinned truth). The other test-time baselines (BM3D, DiffPIR_DiffUNet) need a
-second pretrained network or a package that is not here; they raise a clear error instead of silently running something else. (A second pretrained network sits outside this
+with deepinv unpinned, tests/dps_ref.py is the pinned truth) and "BM3D" (models/bm3d.py: the classical non-learned
+deblurring baseline, two regularised inversions each followed by a BM3D stage under coloured noise, restated because the
+bm3d package is not here; block matching and the two collaborative filters on the sei_bm3d_* kernels; no weights and no flag;
+it needs a physics with a blur kernel; parity with the package unpinned, tests/bm3d_ref.py is the pinned truth). The last
+test-time baseline (DiffPIR_DiffUNet) needs a second pretrained diffusion network; it raises a clear error instead of
+silently running something else. (A second pretrained network sits outside this
 factory: the AlexNet features of the LPIPS metric, metrics.LPIPS, five convolutions whose two small published weight files
 the user names to test.py.)
 """
@@ -32,6 +36,7 @@ from torch.nn import Module
 
 from physics import _bands
 from physics._ops import SeparableResampleOp, apply_linear
+from .bm3d import BM3D
 from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
 from .diffpir import DiffPIR
@@ -41,7 +46,7 @@ from .drunet import DRUNet
 from .pnp import PnPModel
 from .tv import TV
 
-_OUT_OF_SCOPE = ("BM3D", "DiffPIR_DiffUNet")
+_OUT_OF_SCOPE = ("DiffPIR_DiffUNet",)
 
 
 class Identity(Module):
@@ -151,6 +156,8 @@ class Model(Module):
                                           "them, stays outside what this build can run")
             self.model = DPS(physics=physics, denoiser=DRUNet.from_file(weights, device),
                              max_iter=blueprint[DPS.__name__]["max_iter"])
+        elif kind == "BM3D":                                  # reference :123-124: sigma_psd = noise_level / 255
+            self.model = BM3D(physics=physics, sigma_psd=noise_level / 255)
         elif kind in _OUT_OF_SCOPE:
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
                                       "hot path this build implements")

@@ -26,8 +26,11 @@ on the sei_dps_* kernels: the heaviest path of this driver). `--ssim` (build-sid
 `SSIM:`, `SSIM std:` and `METRICS_i` lines; without it they print nan, as before. `--lpips_backbone FILE --lpips_linear FILE`
 (build-side addition; both or neither) name a torchvision AlexNet state dict and the LPIPS v0.1 `alex` linear layers: the
 `LPIPS:`, `LPIPS std:` and `LIPS:` fields then carry metrics.lpips_fn's values (the sei_lpips_* kernels); without them they
-print nan (the pretrained weights are not part of this build and are never fetched). Out of scope and refused: the BM3D / DiffPIR_DiffUNet
-baselines (a second pretrained network or the bm3d package).
+print nan (the pretrained weights are not part of this build and are never fetched). `--model_kind BM3D` (models/bm3d.py: the
+classical deblurring baseline, restated because the bm3d package is not here; two regularised inversions in torch.fft, each
+followed by block matching and a collaborative filter on the sei_bm3d_* kernels; no weights and no flag of its own; it needs a
+physics with a blur kernel, so --task sr and a folder of measurements are refused). Out of scope and refused: the
+DiffPIR_DiffUNet baseline (a second pretrained diffusion network).
 """
 import os
 import sys
