@@ -43,7 +43,8 @@ extern "C" {
  *   U-Net (f32)  sei_conv3x3_fwd, sei_conv3x3_bwd_weight, sei_dwconv7_fwd, sei_dwconv7_bwd_weight (+ _workspace),
  *                sei_ln_fwd, sei_ln_bwd (+ sei_ln_bwd_workspace), sei_gemm_f32, sei_colsum_f32, sei_sepmap2
  *   U-Net (bf16) sei_cast_bf16, sei_ln_fwd_bf16, sei_gemm_bf16nt
- *   optimizer    sei_adam_fused, sei_sgd_fused (+ sei_sgd_partials, sei_sgd_penalty_finish)
+ *   optimizer    sei_adam_fused, sei_sgd_fused (+ sei_sgd_partials, sei_sgd_penalty_finish), sei_adam_anchor_fused
+ *                (+ sei_adam_anchor_partials)
  *   baselines    sei_tv_prox (+ sei_tv_prox_work_floats), sei_bm3d_match (+ sei_bm3d_ref_blocks), sei_bm3d_ht,
  *                sei_bm3d_wiener, sei_bm3d_finish
  * INTERNAL -- everything else in this header: fused, schedule-specific (_ex, _ws, _dw2*, _plan, _eligible, _parts,
@@ -885,6 +886,27 @@ size_t sei_sgd_partials(size_t lo, size_t hi, int grid_cap);
 int sei_sgd_fused(float *param, const float *grad, const float *anchor, const float *coef64, size_t lo, size_t hi,
                   float lr, float grad_scale, uint16_t *param_bf16, double *partials, int grid_cap, void *stream);
 int sei_sgd_penalty_finish(const double *partials, size_t count, float *penalty, void *stream);
+
+/* The same step with torch.optim.Adam's update (--fine_tuning --optimizer Adam; amsgrad=False, coupled weight decay) over
+ * elements [lo, hi) of the bucket: pointers are the BUCKET's (element 0), exp_avg and exp_avg_sq included, and coef64 is
+ * indexed by the absolute block (element >> 6). Per element, float32, in this order (the library is built without
+ * contraction, so the order is the contract):
+ *   g' = grad_scale * g;  with an anchor: d = p - anchor;  g' = g' + (2 c) d;  penalty += (double)((c d) d)  (the p
+ *   before the update);  then sei_adam_fused's update of (p, exp_avg, exp_avg_sq) from g', with lr / (1 - beta1^step) and
+ *   1 / sqrt(1 - beta2^step) derived as sei_adam_fused derives them (double pow and sqrt, rounded once).
+ * Without an anchor, and where p == anchor, the results are sei_adam_fused's bit for bit. exp_avg, exp_avg_sq, p and
+ * (optional) the bf16 copy of the updated p are written in the same pass: 34 bytes per element with anchor and copy,
+ * sei_adam_fused moves 30. Nothing outside [lo, hi) is read or written. Gradients are float32 only.
+ * Argument rules are sei_sgd_fused's: anchor, coef64 and partials together or not at all; lo, hi multiples of 4, and of
+ * 64 with an anchor; float streams 16-byte aligned, param_bf16 8, partials 8; step >= 1; grid_cap >= 0; anything else is
+ * SEI_ERR_BAD_ARG and nothing is launched. Workgroup w writes its penalty sum to partials[w] from the same fixed shuffle
+ * tree (sei_adam_anchor_partials(lo, hi, grid_cap) of them, sei_sgd_partials' values); sei_sgd_penalty_finish folds the
+ * partials of one or several launches. */
+size_t sei_adam_anchor_partials(size_t lo, size_t hi, int grid_cap);
+int sei_adam_anchor_fused(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, const float *anchor,
+                          const float *coef64, size_t lo, size_t hi, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int step, float grad_scale, uint16_t *param_bf16, double *partials,
+                          int grid_cap, void *stream);
 
 /* The same two-segment weight gradient STORED as bf16 (whole-row 8-byte quads): with several GPUs and a bf16-compressed
  * gradient exchange the gradient is written straight into the exchange buffer (parallel.FlatGradientReducer.comm) --

@@ -145,6 +145,7 @@ SIGNATURES = {
     "sei_adam_scalars_to_device": [_F, _F, _F, _F, _F, _I, _P, _P],
     "sei_sgd_fused": [_P, _P, _P, _P, _Z, _Z, _F, _F, _P, _P, _I, _P],
     "sei_sgd_penalty_finish": [_P, _Z, _P, _P],
+    "sei_adam_anchor_fused": [_P, _P, _P, _P, _P, _P, _Z, _Z, _F, _F, _F, _F, _F, _I, _F, _P, _P, _I, _P],
     "sei_drunet_conv3x3": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "sei_drunet_conv3x3_ex": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "sei_drunet_down": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
@@ -246,6 +247,7 @@ SIZE_QUERIES = {
     "sei_sepmap2_small_eligible": [_I, _I, _I, _I, _I, _I],
     "sei_cast_bf16_colsum_parts_count": [_I, _I],
     "sei_sgd_partials": [_Z, _Z, _I],
+    "sei_adam_anchor_partials": [_Z, _Z, _I],
     "sei_drunet_work_bytes": [_I, _I, _I],
     "sei_cg_partials": [_Z],
     "sei_dps_partials": [_I, _Z],

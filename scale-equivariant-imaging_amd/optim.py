@@ -3,6 +3,7 @@
 FlatAdam replaces torch.optim.Adam at demo/train.py:157-186 (same update rule, one kernel launch per chunk instead of a
 foreach sweep per tensor); FlatSGD replaces the fine-tuning path's torch.optim.SGD together with the weights-distance
 penalty that the reference adds to the loss before backward() (demo/train.py:245-266, src/losses/weights_distance_loss.py).
+FlatAdam takes the same penalty and frozen ranges (`anchor`, `only`) for --fine_tuning --optimizer Adam on one GPU.
 
 Keeps a torch.optim.Optimizer-compatible surface (param_groups with "lr", state_dict / load_state_dict,
 zero_grad, step) so the reference's schedulers and checkpoint code drive it unchanged. `state_dict()` is
@@ -18,24 +19,51 @@ import _native as N
 
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, reducer=None,
-                 shard_step=True):
+                 shard_step=True, anchor=None, lambd=1.0, only=None, grid_cap=0):
         """reducer: parallel.FlatGradientReducer under several GPUs. shard_step: with the reducer's "rs_ag" exchange,
         take the optimizer step on this rank's 1 / world share of every chunk only and all-gather the UPDATED weights
         instead of the reduced gradients (`_step_sharded`): the same bytes on the wire, 1 / world of the 30 bytes per
-        parameter that Adam moves through HBM (19.4 GB per step for the default U-Net: 2.4 GB per rank at 8 GPUs)."""
+        parameter that Adam moves through HBM (19.4 GB per step for the default U-Net: 2.4 GB per rank at 8 GPUs).
+        anchor, lambd, only, grid_cap: FlatSGD's fine-tuning arguments with FlatSGD's meaning (--fine_tuning --optimizer
+        Adam): with `anchor=True` the weights at construction are kept, the weights-distance penalty's gradient joins
+        the step and its value -- from the weights BEFORE the update -- is left in `last_penalty` (0-dim, on the device;
+        zero without an anchor); `only`: parameter names, the step then covers their 64-aligned bucket ranges alone and
+        nothing else is read or written, moments and bf16 copy included, and `state_dict()` speaks
+        torch.optim.Adam([those parameters])'s layout (K stays the number of ALL named parameters). Either one sends
+        the step through sei_adam_anchor_fused, one launch per range, and sei_sgd_penalty_finish."""
         backbone = model.get_backbone() if hasattr(model, "get_backbone") else model
         if getattr(backbone, "flat_params", None) is None:
             raise ValueError("FlatAdam needs a model whose parameters live in one flat bucket")
+        if (anchor or only is not None) and reducer is not None:
+            raise ValueError("FlatAdam: the gradient exchange's step (per chunk, sharded across ranks) knows no penalty and "
+                             "no frozen range; anchor / only need the complete gradient on one GPU (reducer=None)")
         self.backbone = backbone
         self.reducer = reducer
         if reducer is not None and reducer.mode == "rs_ag" and shard_step:
             reducer.mode = "sharded"
             start = getattr(backbone, "flat_shadow_only_start", None)
             reducer.set_splits([start] if start is not None else [])
-        self._named = list(model.parameters())        # the order torch.optim.Adam(model.parameters()) indexes by
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        super().__init__([backbone.flat_params], defaults)
         flat = backbone.flat_params
+        self._ranges = None                           # None: the whole bucket through sei_adam_fused
+        if only is None:
+            self._named = list(model.parameters())    # the order torch.optim.Adam(model.parameters()) indexes by
+        else:
+            self._named = [model.get_parameter(key) for key in only]
+            self._ranges = sorted((p._sei_bucket_offset, p._sei_bucket_offset + (p.numel() + 63) // 64 * 64)
+                                  for p in self._named)
+        if anchor and only is None:
+            self._ranges = [(0, flat.numel())]
+        if self._ranges is not None and any(lo % 64 or hi % 64 or hi > flat.numel() for lo, hi in self._ranges):
+            raise ValueError("FlatAdam: a parameter range is not made of whole 64-element blocks of the flat bucket")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__([flat], defaults)
+        self.lambd = float(lambd)
+        self.grid_cap = int(grid_cap)                 # 0: the library's grid (tests and tools/exp_sgd.py pass others)
+        self.anchor = self.coef64 = self._partials = None
+        self.last_penalty = torch.zeros((), dtype=torch.float32, device=flat.device)
+        if anchor:
+            self.anchor = flat.detach().clone()
+            self.coef64 = coefficient_table(model, lambd).to(flat.device)
         self.state[flat] = {"step": 0, "exp_avg": torch.zeros_like(flat), "exp_avg_sq": torch.zeros_like(flat)}
         # optimizer step inside the weight-gradient GEMMs (fuse_weight_updates): slices of the bucket stepped there,
         # the step number the device scalars were prepared for, and whether an eager backward pass filled the bucket
@@ -64,6 +92,9 @@ class FlatAdam(torch.optim.Optimizer):
         models._wgrad.set_fused_adam."""
         if self.reducer is not None:
             raise ValueError("fused weight updates need the complete gradient on this GPU (no gradient exchange)")
+        if self._ranges is not None:
+            raise ValueError("fused weight updates: the GEMM epilogue's Adam knows no weights-distance penalty and no "
+                             "frozen range (FlatAdam with anchor / only steps through sei_adam_anchor_fused alone)")
         from models import _ops
         flat, grads = self.backbone.flat_params, self.backbone.flat_grads
         st = self.state[flat]
@@ -241,6 +272,8 @@ class FlatAdam(torch.optim.Optimizer):
         flat, grads = self.backbone.flat_params, self.backbone.flat_grads
         N.check_tensor(flat, "flat_params")
         group, st = self.param_groups[0], self.state[flat]
+        if self._ranges is not None:
+            return self._step_ranges(flat, grads, group, st)
         st["step"] += 1
         # not a replayed step: fine after zero_grad() + an eager backward pass (a short last batch), which wrote every
         # gradient the ordinary way (the step then covers the WHOLE bucket); anything else would step the fused weights on
@@ -278,6 +311,31 @@ class FlatAdam(torch.optim.Optimizer):
                 update(s, e, grads[s:e], grads.dtype == torch.bfloat16)
         # bf16 weight shadows must be rebuilt before the next forward (the plain copy just was, if asked)
         _ops.weights_updated(self.backbone, plain_shadow_written=shadow is not None)
+
+    def _step_ranges(self, flat, grads, group, st):
+        """The fine-tuning step (anchor and / or `only`): sei_adam_anchor_fused per range, then the penalty's finish."""
+        from models import _ops
+        backbone = self.backbone
+        N.check_tensor(grads, "flat_grads")
+        shadow = getattr(backbone, "flat_shadow", None) if _ops.get_compute_dtype(backbone) == "bf16" else None
+        if shadow is not None and self._ranges != [(0, flat.numel())] and not _ops.plain_shadow_is_current(backbone):
+            _ops.refresh_plain_shadow(backbone)       # this step writes its own ranges of the bf16 copy only
+        st["step"] += 1
+        b1, b2 = group["betas"]
+        counts = [N.lib().sei_adam_anchor_partials(lo, hi, self.grid_cap) for lo, hi in self._ranges]
+        if self.anchor is not None and (self._partials is None or self._partials.numel() < sum(counts)):
+            self._partials = torch.zeros(sum(counts), dtype=torch.float64, device=flat.device)
+        done = 0
+        for (lo, hi), count in zip(self._ranges, counts):
+            N.call("sei_adam_anchor_fused", flat.data_ptr(), grads.data_ptr(), st["exp_avg"].data_ptr(),
+                   st["exp_avg_sq"].data_ptr(), N.ptr(self.anchor), N.ptr(self.coef64), lo, hi, float(group["lr"]),
+                   float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), int(st["step"]), 1.0,
+                   N.ptr(shadow), None if self.anchor is None else self._partials.data_ptr() + 8 * done, self.grid_cap)
+            done += count
+        if self.anchor is not None:
+            N.call("sei_sgd_penalty_finish", self._partials.data_ptr(), done, self.last_penalty.data_ptr())
+        # bf16 weight shadows must be rebuilt before the next forward (the plain copy just was, if asked)
+        _ops.weights_updated(backbone, plain_shadow_written=shadow is not None)
 
 
 def coefficient_table(model, lambd=1.0):

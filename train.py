@@ -21,8 +21,10 @@ step runs in libsei_hip.so. Differences, all build-side and documented in DESIGN
   * `--fine_tuning` (demo/train.py:95-114, 144-186, 245-264): `--dataset DIR` trains on the measured PNGs of a folder
     (one random crop per file, kept on the device), the defaults become SGD at 1e-2, `--weights_distance_loss` keeps the
     weights near the loaded ones and `--fine_tuning_params` steps SwinIR's `conv_last` alone. With `--fused_optimizer`
-    the SGD step and the penalty are one fused kernel (optim.FlatSGD) and the step replays from a hipGraph; with
-    `--no-fused_optimizer` it is the reference's literal sequence (losses/weights_distance_loss.py + torch.optim.SGD).
+    the SGD step and the penalty are one fused kernel (optim.FlatSGD) and the step replays from a hipGraph; so are,
+    on one GPU, `--optimizer Adam`'s step and penalty (optim.FlatAdam with an anchor or frozen ranges; under several
+    GPUs Adam with either fine-tuning option stays torch's own). With `--no-fused_optimizer` it is the reference's
+    literal sequence (losses/weights_distance_loss.py + torch.optim.SGD / torch.optim.Adam).
     The reference's assertions are ValueErrors raised before anything touches the GPU; `--fine_tuning_params` with the
     Convolutional architecture, which has no `conv_last`, is one of them (the reference dies in `get_parameter`).
 """
@@ -227,9 +229,12 @@ def main(argv=None):
 
     from models import _ops as model_ops
     model_ops.set_compute_dtype(args.compute_dtype)
-    # FlatAdam steps the whole bucket and knows no penalty: with either fine-tuning option Adam is torch's own
-    fused_adam = optimizer_kind == "Adam" and args.fused_optimizer and not (args.fine_tuning_params
-                                                                            or args.weights_distance_loss)
+    # FlatAdam's penalty and frozen ranges need the complete gradient on this GPU (sei_adam_anchor_fused); the exchange's
+    # per-chunk and sharded steps know neither: under several GPUs Adam with either fine-tuning option is torch's own
+    fine_tuning_option = bool(args.fine_tuning_params or args.weights_distance_loss)
+    fused_adam = optimizer_kind == "Adam" and args.fused_optimizer and not fine_tuning_option
+    fused_adam_fine_tuning = (optimizer_kind == "Adam" and args.fused_optimizer and fine_tuning_option
+                              and not parallel.exchange_active())
     if args.grad_comm_dtype == "bf16" and not fused_adam:
         raise ValueError("--grad_comm_dtype bf16 needs the fused Adam (it reads the bf16 bucket directly)")
     comm_dtype = torch.bfloat16 if args.grad_comm_dtype == "bf16" else torch.float32
@@ -239,6 +244,9 @@ def main(argv=None):
     params = model.parameters() if only is None else [model.get_parameter(key) for key in only]
     if fused_adam:
         optimizer = FlatAdam(model, lr=lr, betas=(0.9, args.optimizer_beta2), reducer=reducer)
+    elif fused_adam_fine_tuning:
+        optimizer = FlatAdam(model, lr=lr, betas=(0.9, args.optimizer_beta2),
+                             anchor=args.weights_distance_loss or None, lambd=1.0, only=only)
     elif optimizer_kind == "Adam":
         optimizer = torch.optim.Adam(params, lr=lr, betas=(0.9, args.optimizer_beta2))
     elif optimizer_kind == "SGD" and args.fused_optimizer:
@@ -271,7 +279,7 @@ def main(argv=None):
         assert args.lr is not None
         for group in optimizer.param_groups:
             group["lr"] = args.lr
-        if isinstance(optimizer, FlatSGD) and optimizer.anchor is not None:
+        if getattr(optimizer, "anchor", None) is not None:    # FlatSGD / FlatAdam with the penalty folded in
             optimizer.anchor.copy_(backbone.flat_params)      # as upstream: the penalty's anchor is the resumed model
 
     checkpoints_dir = f"{args.out_dir}/checkpoints"
@@ -291,9 +299,11 @@ def main(argv=None):
                             state_path=checkpoint_name(0))
 
     # the reference's literal penalty (a deepcopy of the model as it stands here, added to the loss before backward()):
-    # every optimizer but FlatSGD, whose kernel applies the same penalty and leaves its value in `last_penalty`
+    # every optimizer but FlatSGD and the fine-tuning FlatAdam, whose kernels apply the same penalty and leave its value in
+    # `last_penalty`
+    fused_penalty = isinstance(optimizer, FlatSGD) or fused_adam_fine_tuning
     weights_distance = None
-    if args.weights_distance_loss and not isinstance(optimizer, FlatSGD):
+    if args.weights_distance_loss and not fused_penalty:
         from losses.weights_distance_loss import WeightsDistanceLoss
         weights_distance = WeightsDistanceLoss(pretrained_model=model, lambd=1, device=args.device)
 
@@ -318,7 +328,8 @@ def main(argv=None):
                                               (args.batch_size, y.shape[1], args.Loss__crop_size, args.Loss__crop_size),
                                               early_release=early,
                                               fuse_optimizer=(reducer is None and args.fuse_optimizer_step
-                                                              and isinstance(optimizer, FlatAdam)))
+                                                              and isinstance(optimizer, FlatAdam)
+                                                              and not fused_adam_fine_tuning))
                     if early and graphed.early_grads is not None:
                         early_event = graphed.early_grads[0]
                         # (a capture after sharded optimizer steps -- the first batches were short -- changes which
@@ -345,7 +356,7 @@ def main(argv=None):
                     backbone.flat_grads /= world
             optimizer.step()
             loss_sum += training_loss.detach()
-            if isinstance(optimizer, FlatSGD):
+            if fused_penalty:
                 loss_sum += optimizer.last_penalty            # the logged loss includes the penalty, as upstream
             steps += 1
             if args.max_steps is not None and steps >= args.max_steps:
