@@ -120,8 +120,15 @@ def layer_norm_bwd(x2d, gamma, mean, rstd, gy, ggamma, gbeta, res=None):
 
 
 def colsum_into(acc, x2d, row_weight=None):
-    """acc[n] += sum_m x2d[m, n] (times row_weight[m] if given): a bias gradient."""
+    """acc[n] += sum_m x2d[m, n] (times row_weight[m] if given): a bias gradient. The kernels take a pointer and (M, N):
+    rows N floats apart, N accumulators, M weights. Anything else (a column slice of a wider matrix, an accumulator of
+    another length) is refused here: the kernels would sum, or add to, other memory."""
     M, Nn = x2d.shape
+    if not x2d.is_contiguous() or not acc.is_contiguous() or acc.numel() != Nn:
+        raise ValueError(f"colsum_into: expected contiguous (M, N) rows and N contiguous accumulators, got rows of shape "
+                         f"{tuple(x2d.shape)} and strides {x2d.stride()}, accumulators of shape {tuple(acc.shape)}")
+    if row_weight is not None and (not row_weight.is_contiguous() or row_weight.numel() != M):
+        raise ValueError(f"colsum_into: expected {M} contiguous row weights, got shape {tuple(row_weight.shape)}")
     if row_weight is None:
         N.call("sei_colsum_f32", x2d.data_ptr(), acc.data_ptr(), M, Nn)
     else:

@@ -10,6 +10,8 @@ Plain torch on the CPU: nothing of the library under test is imported here. Thre
            max-norm relative deviation from float64, and a kernel must sit within max(FLOOR, 3 * ref32) of float64
            relative to max |ref64| (the rule of tests/test_transform_edges_gpu.py). Column sums and LayerNorm parameter
            gradients take REDUCTION_FLOOR instead. The factor 3 is the margin for another summation order.
+           (`hold32_on`: the same rule on a scale the caller names -- the sum of the absolute terms of a sum that
+           cancels; tests/loss_reduction_ref.py.)
   bf16     (`hold_bf16`) per element |got - ref64| <= 2^-8 |ref64| + e32: the largest half-ulp of a round-to-nearest bf16
            value relative to it, and e32 = three times the float32 chain's max ABSOLUTE deviation on the same input.
 
@@ -62,6 +64,20 @@ def hold32_abs(label, got, r64, r32, floor=FLOOR):
     return err, ref32
 
 
+def hold32_on(label, got, r64, r32, scale, floor=FLOOR):
+    """The same rule on a given scale: |got - r64| <= max(floor, 3 * ref32) * scale, ref32 = |r32 - r64| / scale. For a sum
+    whose terms cancel, `scale` is the float64 sum of the absolute terms: the size of what the kernel added up, where
+    max |r64| would be the size of what the inputs left over. Prints and returns (deviation, ref32), both on that scale."""
+    got, r64, r32 = got.detach().cpu().double(), r64.double(), r32.double()
+    scale = float(scale)
+    assert got.shape == r64.shape and bool(torch.isfinite(r64).all()) and scale >= 0, label
+    scale = max(scale, 1e-300)
+    ref32, err = float((r32 - r64).abs().max()) / scale, float((got - r64).abs().max()) / scale
+    print(f"{label}: err {err:.2e} of the scale {scale:.3e}, ref32 {ref32:.2e}, bar {bar(ref32, floor):.2e}")
+    assert err <= bar(ref32, floor), (label, err, ref32)
+    return err, ref32
+
+
 def hold_bf16(label, got, r64, r32):
     """bf16 results of float32 arithmetic, per element; prints and returns (worst excess over 2^-8 |ref64|, e32)."""
     got, r64 = got.detach().cpu().double(), r64.double()
@@ -108,6 +124,14 @@ def nan_tailed(t, device="cuda"):
     flat = torch.full((t.numel() + MARGIN,), float("nan") if t.is_floating_point() else -1, dtype=t.dtype, device=device)
     flat[:t.numel()] = t.reshape(-1).to(device)
     return flat[:t.numel()].view(t.shape)
+
+
+def nan_framed(t, lead, device="cuda"):
+    """nan_tailed with `lead` NaNs in front as well: a contiguous copy of `t` that starts `lead` elements into its
+    allocation (lead = 1: 4 bytes off the 16-byte grid for float32)."""
+    flat = torch.full((lead + t.numel() + MARGIN,), float("nan"), dtype=t.dtype, device=device)
+    flat[lead:lead + t.numel()] = t.reshape(-1).to(device)
+    return flat[lead:lead + t.numel()].view(t.shape)
 
 
 # ---------------------------------------------------------------------------------------------- padded grid
