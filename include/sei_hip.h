@@ -1191,6 +1191,50 @@ int sei_bm3d_wiener(const float *noisy, const float *pilot, const float *var, co
                     int H, int W, int step, int n_max, int window, int agg, float *work, void *stream);
 int sei_bm3d_finish(const float *work, float *out, int planes, int H, int W, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The diffusion U-Net of the DiffPIR_DiffUNet baseline (models/diffunet.py; csrc/adm_kernels.hip): guided-diffusion's
+ * "ADM" network as deepinv's DiffUNet(large_model=False) builds it, restated in models/diffunet.py and pinned by
+ * tests/diffunet_ref.py. The layout is the DRUNet family's: float32 rows (R, C) on the row indexing of the zero-bordered
+ * grid (B, H + 2, W + 2), R = B (H + 2) (W + 2); bf16 grids of the same rows with W + 3 guard rows in front and behind,
+ * every grid pointer ROW 0 of its grid; bf16 weights (N, taps * Cin), tap t = 3 ky + kx. Only interior rows are read and
+ * written (sei_adm_pack_image writes its whole grid): the border of a bf16 grid stays as the caller zeroed it, guard rows
+ * are read by the 3x3 convolution but never written and never reach a result. No split-K and no atomics anywhere: the same
+ * bits on every run and at every batch position. Pointers 16-byte aligned (statistics and NCHW images: 4).
+ * An input "Xa | Xb" is the channel concatenation of two float32 buffers of Ca and Cb channels (Xb NULL with Cb = 0);
+ * Ca, Cb multiples of 4, Ca + Cb a multiple of 128: 32 groups of a multiple of 4 channels, which may straddle the seam.
+ *   sei_adm_gn_stats    stats[b][g] = (mean, 1 / sqrt(var + eps)) of group g of image b, biased variance, two passes in
+ *                       float32 (a first mean m0, then the distances d from it: mean = m0 + E[d], M2 = sum d^2 - n E[d]^2)
+ *                       per slice of 1024 pixels, one workgroup per (b, g, slice); above one slice a second launch
+ *                       merges the slices' (mean, M2) from `part` in a fixed order. part: B sei_adm_gn_part_floats(H, W)
+ *                       floats (0 = extents refused); the launch shape depends on the extents only.
+ *   sei_adm_gn_apply    v = SiLU(((x - mean) rstd gamma + beta) [* (1 + mod[b][c]) + mod[b][C + c]]) with mod (B, 2 C) or
+ *                       NULL; silu 0 leaves the SiLU out (attention's norm); stats NULL (then gamma, beta, mod NULL):
+ *                       v = x. resample 0: written at the input's extents; 1: the 2x2 average of v into the (H / 2, W / 2) grid (H, W even); 2: v repeated 2x into the
+ *                       (2 H, 2 W) grid. Y16 (a bf16 grid) and / or Y32 (float32 rows) of the OUTPUT's extents; H, W are
+ *                       the input's.
+ *   sei_adm_pack_image  x (B, 3, H, W) float32 NCHW -> the head's bf16 grid of 32 channels (x, zeros), borders zero.
+ *   sei_adm_conv        v = (conv(X) + bias) [+ T_res]; T_out = v and / or Y16 = bf16(v), at least one. ntaps 9 (3x3, zero
+ *                       padding 1) or 1 (1x1); Cin a multiple of 32, Cout of 64. T_out may be T_res.
+ *   sei_adm_tail        out (B, 3, H, W) float32 NCHW = conv3x3(X) + bias: Wt (16, 9 Cin) and bias (16) with zeros behind
+ *                       the third row / entry.
+ *   sei_adm_attention   QKV16 bf16 rows (R, 3 C): head h of C / 64 owns channels [192 h, 192 h + 64) as q, the next 64 as
+ *                       k, the next 64 as v. A16 (R, C) bf16, channels [64 h, 64 h + 64) = softmax_s((q_t . k_s) / 8) v_s
+ *                       over the T = H W interior rows of the image: bf16 MFMA products, the row maximum subtracted, the
+ *                       running maximum and sum in float32, the probabilities rounded to bf16 ahead of the second product.
+ *                       Any T >= 1. */
+size_t sei_adm_gn_part_floats(int H, int W);
+int sei_adm_gn_stats(const float *Xa, int Ca, const float *Xb, int Cb, int B, int H, int W, float eps, float *stats,
+                     float *part, void *stream);
+int sei_adm_gn_apply(const float *Xa, int Ca, const float *Xb, int Cb, const float *stats, const float *gamma,
+                     const float *beta, const float *mod, int silu, int B, int H, int W, int resample, uint16_t *Y16,
+                     float *Y32, void *stream);
+int sei_adm_pack_image(const float *x, uint16_t *G16, int B, int H, int W, void *stream);
+int sei_adm_conv(const uint16_t *X, const uint16_t *Wt, const float *bias, int Cin, int Cout, int ntaps, int B, int H, int W,
+                 const float *T_res, float *T_out, uint16_t *Y16, void *stream);
+int sei_adm_tail(const uint16_t *X, const uint16_t *Wt, const float *bias, int Cin, int B, int H, int W, float *out,
+                 void *stream);
+int sei_adm_attention(const uint16_t *QKV16, int C, int B, int H, int W, uint16_t *A16, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,12 @@ SIGNATURES = {
     "sei_bm3d_ht": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _c.c_double, _I, _P, _P, _P],
     "sei_bm3d_wiener": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "sei_bm3d_finish": [_P, _P, _I, _I, _I, _P],
+    "sei_adm_gn_stats": [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P],
+    "sei_adm_gn_apply": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "sei_adm_pack_image": [_P, _P, _I, _I, _I, _P],
+    "sei_adm_conv": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "sei_adm_tail": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "sei_adm_attention": [_P, _I, _I, _I, _I, _P, _P],
 }
 
 _lib = None
@@ -252,6 +258,7 @@ SIZE_QUERIES = {
     "sei_cg_partials": [_Z],
     "sei_dps_partials": [_I, _Z],
     "sei_bm3d_ref_blocks": [_I, _I, _I],
+    "sei_adm_gn_part_floats": [_I, _I],
 }
 ABI_VERSION = 12      # SEI_ABI_VERSION of include/sei_hip.h this table was written against
 

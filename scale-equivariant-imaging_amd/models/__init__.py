@@ -23,9 +23,13 @@ transposed weights and sei_drunet_conv3x3_masked -- and the sei_dps_* step kerne
 with deepinv unpinned, tests/dps_ref.py is the pinned truth) and "BM3D" (models/bm3d.py: the classical non-learned
 deblurring baseline, two regularised inversions each followed by a BM3D stage under coloured noise, restated because the
 bm3d package is not here; block matching and the two collaborative filters on the sei_bm3d_* kernels; no weights and no flag;
-it needs a physics with a blur kernel; parity with the package unpinned, tests/bm3d_ref.py is the pinned truth). The last
-test-time baseline (DiffPIR_DiffUNet) needs a second pretrained diffusion network; it raises a clear error instead of
-silently running something else. (A second pretrained network sits outside this
+it needs a physics with a blur kernel; parity with the package unpinned, tests/bm3d_ref.py is the pinned truth) and
+"DiffPIR_DiffUNet" (models/diffpir.py's DiffPIRDiffUNet: the same DiffPIR loop, reflect-padded and cropped as the
+reference's wrapper does, around the diffusion U-Net of models/diffunet.py -- guided-diffusion's FFHQ-256 network as deepinv's
+DiffUNet(large_model=False) builds it -- on the sei_adm_* kernels: GroupNorm, biased 3x3 convolutions, resampling blocks
+and global attention; the user names the checkpoint's state dict with --diffunet_weights, nothing is fetched, and without
+the flag the kind raises a clear error instead of silently running something else; --diffpir_iterations applies; parity
+with deepinv unpinned, tests/diffunet_ref.py is the pinned truth). (One more pretrained network sits outside this
 factory: the AlexNet features of the LPIPS metric, metrics.LPIPS, five convolutions whose two small published weight files
 the user names to test.py.)
 """
@@ -39,7 +43,8 @@ from physics._ops import SeparableResampleOp, apply_linear
 from .bm3d import BM3D
 from .convolutional import ConvolutionalModel
 from .swinir import SwinIR
-from .diffpir import DiffPIR
+from .diffpir import DiffPIR, DiffPIRDiffUNet
+from .diffunet import DiffUNet
 from .dip import DeepImagePrior
 from .dps import DPS
 from .drunet import DRUNet
@@ -158,9 +163,18 @@ class Model(Module):
                              max_iter=blueprint[DPS.__name__]["max_iter"])
         elif kind == "BM3D":                                  # reference :123-124: sigma_psd = noise_level / 255
             self.model = BM3D(physics=physics, sigma_psd=noise_level / 255)
-        elif kind in _OUT_OF_SCOPE:
+        elif kind == "DiffPIR_DiffUNet" and blueprint[DiffPIRDiffUNet.__name__]["diffunet_weights"] is not None:
+            if physics is None:                               # reference :127-128: DiffPIR(physics, model="DiffUNet")
+                raise NotImplementedError("model kind 'DiffPIR_DiffUNet' solves its data step with the physics' A and "
+                                          "A_adjoint: it cannot run on a folder of measurements without a physics")
+            weights = blueprint[DiffPIRDiffUNet.__name__]["diffunet_weights"]
+            self.model = DiffPIRDiffUNet(physics=physics, denoiser=DiffUNet.from_file(weights, device), task=task,
+                                         max_iter=blueprint[DiffPIRDiffUNet.__name__]["max_iter"])
+        elif kind in _OUT_OF_SCOPE:                           # the no-weights path of DiffPIR_DiffUNet
             raise NotImplementedError(f"model kind {kind!r} is an evaluation baseline outside the training "
-                                      "hot path this build implements")
+                                      "hot path this build implements unless its pretrained diffusion U-Net is named: "
+                                      "nothing is fetched, give the state dict of the FFHQ checkpoint that deepinv's "
+                                      "DiffUNet(large_model=False) loads with --diffunet_weights")
         else:
             raise ValueError(f"Unknown model kind: {kind}")
         if data_parallel_devices is not None:
@@ -231,6 +245,9 @@ def get_model(args, physics, device):
         DiffPIR.__name__: {"drunet_weights": getattr(args, "drunet_weights", None),
                            "max_iter": 100 if getattr(args, "diffpir_iterations", None) is None
                            else args.diffpir_iterations},
+        DiffPIRDiffUNet.__name__: {"diffunet_weights": getattr(args, "diffunet_weights", None),
+                                   "max_iter": 100 if getattr(args, "diffpir_iterations", None) is None
+                                   else args.diffpir_iterations},
         DPS.__name__: {"drunet_weights": getattr(args, "drunet_weights", None),
                        "max_iter": 1000 if getattr(args, "dps_iterations", None) is None else args.dps_iterations},
         TV.__name__: {"lambd": getattr(args, "tv_lambd", None), "max_iter": getattr(args, "tv_max_iter", None) or 300},

@@ -29,6 +29,12 @@ conjugate gradients with one host read per iteration, and torch expressions for 
 Noise comes from torch's generator, as in the reference, through `draw(i, like)`: i = 0 is the initial noise, i = k + 1
 the noise of sampling step k. `cg_iterations` lists the conjugate-gradient iteration count of every prox of the last
 forward. sigma = 0 makes the data step's gamma infinite and is refused.
+
+The DiffPIR_DiffUNet baseline is `DiffPIRDiffUNet` below: the same loop around the diffusion U-Net of models/diffunet.py
+(deepinv's DiffUNet(large_model=False); the user names its weights with --diffunet_weights), on the wrapper's other path
+(src/models/diffpir.py:26-45): the measurement is reflect-padded at the bottom and right to multiples of 32 for deblurring
+and of 16 otherwise, the loop runs on the padded measurement, and the result is cropped to rate x the unpadded extents.
+The pinned truth of that path is tests/diffunet_ref.py.
 """
 import numpy as np
 import torch
@@ -154,3 +160,44 @@ class DiffPIR(Module):
                 x = float(sa[tn]) * x0 + float(s1m[tn]) * (float(np.sqrt(1 - zeta)) * eps + float(np.sqrt(zeta)) * nz)
                 xin = x / (2 * float(np.sqrt(at_n))) + 0.5
         return x0 / 2 + 0.5
+
+
+def pad_amounts(h, w, task):
+    """Rows and columns the reference's wrapper adds at the bottom and right of an h x w measurement: up to the next
+    multiple of 32 for deblurring, of 16 otherwise (src/models/diffpir.py:28-35)."""
+    m = 32 if task == "deblurring" else 16
+    return (m - h % m) % m, (m - w % m) % m
+
+
+class DiffPIRDiffUNet(DiffPIR):
+    """The DiffPIR_DiffUNet baseline: the reference wrapper's `forward` on its diffusion U-Net path
+    (src/models/diffpir.py:26-45) around the loop above, `denoiser` a models.diffunet.DiffUNet (or any callable
+    (x, sigma) -> x that takes the padded extents). y is reflect-padded at the bottom and right (`pad_amounts`), the loop
+    runs on the padded y, and the result is cropped to rate x the unpadded extents (rate = physics.rate, 1 without one).
+    `task` defaults to physics.task, which physics.get_physics sets. A pad that is not smaller than its axis (reflection
+    has nothing to mirror) raises ValueError. The noise level and the schedule are DiffPIR_DRUNet's."""
+
+    def __init__(self, physics, denoiser, task=None, **kwargs):
+        super().__init__(physics, denoiser, **kwargs)
+        self.task = task if task is not None else getattr(physics, "task", None)
+        if self.task is None:
+            raise ValueError("DiffPIRDiffUNet: the padding depends on the task (deblurring: multiples of 32, otherwise 16); "
+                             "give task= or a physics with a .task")
+
+    def padded_extents(self, h, w):
+        ph, pw = pad_amounts(h, w, self.task)
+        if ph >= h or pw >= w:
+            raise ValueError(f"DiffPIRDiffUNet: a {h} x {w} measurement would be reflect-padded by {ph} x {pw}, which is not "
+                             "smaller than the axis")
+        return h + ph, w + pw
+
+    @torch.no_grad()
+    def forward(self, y):
+        N.check_tensor(y.contiguous() if isinstance(y, torch.Tensor) else y, "y")
+        h, w = y.shape[-2:]
+        hp, wp = self.padded_extents(h, w)
+        if (hp, wp) != (h, w):
+            y = torch.nn.functional.pad(y, (0, wp - w, 0, hp - h), mode="reflect")
+        x = super().forward(y.contiguous())
+        rate = int(getattr(self.physics, "rate", 1) or 1)
+        return x[:, :, :rate * h, :rate * w].contiguous()

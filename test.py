@@ -29,8 +29,11 @@ on the sei_dps_* kernels: the heaviest path of this driver). `--ssim` (build-sid
 print nan (the pretrained weights are not part of this build and are never fetched). `--model_kind BM3D` (models/bm3d.py: the
 classical deblurring baseline, restated because the bm3d package is not here; two regularised inversions in torch.fft, each
 followed by block matching and a collaborative filter on the sei_bm3d_* kernels; no weights and no flag of its own; it needs a
-physics with a blur kernel, so --task sr and a folder of measurements are refused). Out of scope and refused: the
-DiffPIR_DiffUNet baseline (a second pretrained diffusion network).
+physics with a blur kernel, so --task sr and a folder of measurements are refused). `--model_kind DiffPIR_DiffUNet
+--diffunet_weights FILE [--diffpir_iterations N]` (models/diffpir.py's DiffPIRDiffUNet around models/diffunet.py: the same
+DiffPIR loop on the reflect-padded measurement, cropped afterwards as the reference's wrapper does, with the diffusion U-Net
+of deepinv's DiffUNet(large_model=False) on the sei_adm_* kernels as its denoiser; FILE is the state dict of the FFHQ
+checkpoint deepinv fetches, supplied by the user and never fetched here; without the flag the kind raises and names it).
 """
 import os
 import sys
@@ -74,6 +77,7 @@ def build_parser():
     flag("--lpips_backbone", type=str, default=None, metavar="FILE")                     # build-side addition
     flag("--lpips_linear", type=str, default=None, metavar="FILE")                       # build-side addition
     flag("--drunet_weights", type=str, default=None, metavar="FILE")                     # build-side addition
+    flag("--diffunet_weights", type=str, default=None, metavar="FILE")                   # build-side addition
     flag("--diffpir_iterations", type=int, default=100)                                  # build-side addition
     flag("--dps_iterations", type=int, default=1000)                                     # build-side addition
     return parser
