@@ -257,6 +257,23 @@ int sei_sure_loss(const float *y, const float *y1, const float *y2, const float 
                   float *g2, float *work, void *stream);
 int sei_mse_loss(const float *a, const float *b, size_t n, float grad_scale, float value_scale, float *out2, float *ga,
                  float *work, void *stream);
+/* UNSURE (Tachella, Davies, Jacques: SURE with an unknown noise level; restated from the paper): sei_sure_loss with the
+ * constant sigma^2 replaced by a Lagrange multiplier that lives in DEVICE memory and is moved by gradient ascent inside the
+ * call, so that a captured step replays it. state = {eta, m, k, unused} (16-byte aligned): eta stands for sigma^2, m is the
+ * averaged ascent direction, k the number of updates so far (as a float).
+ *   stage 1   sei_sure_loss's with c_div = 2 state[0] inv_n_div read by every workgroup: g1 / g2 carry the multiplier as
+ *             it stood BEFORE this call's update. y1 / y2 and g1 / g2 may be the halves of one 2B-image tensor.
+ *   stage 2   out3 = {div sum, mse sum, c_mse out3[1] + 2 eta d}, d = out3[0] inv_n_div (no constant term); then, if
+ *             `update` (0 or 1): g = 2 d, m' = g when k == 0 else momentum m + (1 - momentum) g, eta' = eta + step_size m',
+ *             k' = k + 1. eta is not clamped. With update == 0 the state is not written.
+ * Refused: what sei_sure_loss refuses, a null or misaligned state, momentum outside [0, 1), a non-finite step_size.
+ * sei_axpy_sqrt_dev: out = a + sqrt(max(*p, 0)) b with p in device memory (the measurement noise of the equivariant branch
+ * at the estimated level); sei_axpy's alignment. */
+int sei_sure_loss_unsure(const float *y, const float *y1, const float *y2, const float *b, int planes, int H, int W,
+                         int margin_div, int margin_mse, float tau, float c_mse, float inv_n_div, float step_size,
+                         float momentum, int update, float *state, float *out3, float *g1, float *g2, float *work,
+                         void *stream);
+int sei_axpy_sqrt_dev(const float *a, const float *b, const float *p, float *out, size_t n, void *stream);
 /* Numerator of the luma PSNR of the evaluation step (reference src/metrics.py:10-13: kornia rgb_to_ycbcr's
  * Y = 0.299 R + 0.587 G + 0.114 B, torchmetrics PSNR with data_range 1): out1[0] = sum over the npix pixels of
  * (Y(a) - Y(b))^2 for planar RGB images a, b of shape (3, npix). `work` holds SEI_REDUCE_BLOCKS floats. */

@@ -5,14 +5,20 @@
 //   sei_axpy       : y + sigma*n (deepinv GaussianNoise), y + tau*b (losses/sure.py:24)
 //   sei_sure_terms : losses/sure.py:24-31 (mc_div) and :57-62 (cropped mse) + d/dy1, d/dy2
 //   sei_mse_terms  : deepinv `mse` metric inside EILoss (losses/__init__.py:117-122) + d/dx3
+//   sei_sure_loss_unsure : losses/sure.py:24-31,57-66 with sigma^2 replaced by a device-resident multiplier and its ascent
+//                    step (UNSURE, Tachella, Davies, Jacques; restated from the paper, no reference lines: the reference's
+//                    sure.py predates it)
+//   sei_axpy_sqrt_dev : y + sqrt(max(eta, 0))*n, deepinv GaussianNoise with the multiplier read from device memory
+#include <cmath>
+
 #include "sei_common.h"
 
 namespace {
 
 constexpr int RED_THREADS = 256;
 
-__global__ __launch_bounds__(256) void axpy_kernel(const float *__restrict__ a, const float *__restrict__ b,
-                                                   float alpha, float *__restrict__ out, size_t n) {
+__device__ __forceinline__ void axpy_body(const float *__restrict__ a, const float *__restrict__ b, float alpha,
+                                          float *__restrict__ out, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t n4 = n / 4;
     const float4 *a4 = reinterpret_cast<const float4 *>(a);
@@ -27,12 +33,23 @@ __global__ __launch_bounds__(256) void axpy_kernel(const float *__restrict__ a, 
         out[i] = fmaf(alpha, b[i], a[i]);
 }
 
+__global__ __launch_bounds__(256) void axpy_kernel(const float *__restrict__ a, const float *__restrict__ b,
+                                                   float alpha, float *__restrict__ out, size_t n) {
+    axpy_body(a, b, alpha, out, n);
+}
+
+// alpha = sqrt(max(*p, 0)) read from device memory by every thread (one cached scalar load): the UNSURE noise level
+__global__ __launch_bounds__(256) void axpy_sqrt_dev_kernel(const float *__restrict__ a, const float *__restrict__ b,
+                                                            const float *__restrict__ p, float *__restrict__ out,
+                                                            size_t n) {
+    axpy_body(a, b, sqrtf(fmaxf(*p, 0.f)), out, n);
+}
+
 // stage 1: per-block partial sums of the two SURE terms + elementwise gradients
-__global__ __launch_bounds__(RED_THREADS) void sure_terms_kernel(
+__device__ __forceinline__ void sure_terms_body(
     const float *__restrict__ y, const float *__restrict__ y1, const float *__restrict__ y2,
     const float *__restrict__ b, size_t total, int H, int W, int md, int mm, float inv_tau, float c_mse,
-    float c_div, float *__restrict__ g1, float *__restrict__ g2, float *__restrict__ work) {
-    __shared__ float scratch[RED_THREADS / 64];
+    float c_div, float *__restrict__ g1, float *__restrict__ g2, float *__restrict__ work, float *scratch) {
     float s_div = 0.f, s_mse = 0.f;
     const size_t stride = (size_t)gridDim.x * RED_THREADS;
     for (size_t i = (size_t)blockIdx.x * RED_THREADS + threadIdx.x; i < total; i += stride) {
@@ -62,6 +79,26 @@ __global__ __launch_bounds__(RED_THREADS) void sure_terms_kernel(
         work[blockIdx.x] = bd;
         work[SEI_REDUCE_BLOCKS + blockIdx.x] = bm;
     }
+}
+
+__global__ __launch_bounds__(RED_THREADS) void sure_terms_kernel(
+    const float *__restrict__ y, const float *__restrict__ y1, const float *__restrict__ y2,
+    const float *__restrict__ b, size_t total, int H, int W, int md, int mm, float inv_tau, float c_mse,
+    float c_div, float *__restrict__ g1, float *__restrict__ g2, float *__restrict__ work) {
+    __shared__ float scratch[RED_THREADS / 64];
+    sure_terms_body(y, y1, y2, b, total, H, W, md, mm, inv_tau, c_mse, c_div, g1, g2, work, scratch);
+}
+
+// stage 1 with c_div = 2 eta / n_div formed from the multiplier in device memory (state[0]; UNSURE): every workgroup reads
+// it before the finishing block of the same call may move it, so the gradients carry the multiplier as it stood
+__global__ __launch_bounds__(RED_THREADS) void sure_terms_unsure_kernel(
+    const float *__restrict__ y, const float *__restrict__ y1, const float *__restrict__ y2,
+    const float *__restrict__ b, size_t total, int H, int W, int md, int mm, float inv_tau, float c_mse,
+    float inv_n_div, const float *__restrict__ state, float *__restrict__ g1, float *__restrict__ g2,
+    float *__restrict__ work) {
+    __shared__ float scratch[RED_THREADS / 64];
+    const float c_div = (2.f * state[0]) * inv_n_div;
+    sure_terms_body(y, y1, y2, b, total, H, W, md, mm, inv_tau, c_mse, c_div, g1, g2, work, scratch);
 }
 
 __global__ __launch_bounds__(RED_THREADS) void mse_terms_kernel(const float *__restrict__ a,
@@ -129,6 +166,38 @@ __global__ __launch_bounds__(RED_THREADS) void finish_loss_kernel(const float *_
     if (threadIdx.x == 0) out[nout] = total;
 }
 
+// stage 2 of the UNSURE loss: the two sums folded as finish_loss_kernel folds them, loss = c_mse mse + 2 eta d with
+// d = div / n_div and eta = state[0] (no constant term), then -- `update` -- one step of gradient ASCENT on the multiplier
+// along the averaged direction: g = 2 d, m' = g on the first call (k == 0) else mu m + (1 - mu) g, eta' = eta + alpha m',
+// k' = k + 1. state = {eta, m, k, unused}; thread 0 alone reads and writes it, with ordinary stores.
+struct UnsureStep {
+    float c_mse, inv_n_div, step_size, momentum;
+    int update;
+};
+__global__ __launch_bounds__(RED_THREADS) void finish_unsure_kernel(const float *__restrict__ work, int nparts, UnsureStep u,
+                                                                    float *__restrict__ state, float *__restrict__ out) {
+    __shared__ float scratch[RED_THREADS / 64];
+    float sums[2];
+    for (int q = 0; q < 2; ++q) {
+        float v = 0.f;
+        for (int i = threadIdx.x; i < nparts; i += RED_THREADS) v += work[q * SEI_REDUCE_BLOCKS + i];
+        sums[q] = sei_block_sum<RED_THREADS>(v, scratch);    // (only thread 0's value is the block sum; only it goes on)
+    }
+    if (threadIdx.x != 0) return;
+    const float eta = state[0], m = state[1], k = state[2];
+    const float d = sums[0] * u.inv_n_div;
+    out[0] = sums[0];
+    out[1] = sums[1];
+    out[2] = fmaf(u.c_mse, sums[1], (2.f * eta) * d);
+    if (u.update) {
+        const float g = 2.f * d;
+        const float m_new = k == 0.f ? g : fmaf(u.momentum, m, (1.f - u.momentum) * g);
+        state[0] = fmaf(u.step_size, m_new, eta);
+        state[1] = m_new;
+        state[2] = k + 1.f;
+    }
+}
+
 inline int reduce_blocks(size_t n) {
     size_t g = sei_ceil_div(n, (size_t)RED_THREADS * 4);
     if (g < 1) g = 1;
@@ -174,6 +243,15 @@ extern "C" int sei_axpy(const float *a, const float *b, float alpha, float *out,
     size_t grid = sei_ceil_div(n / 4 + 1, 256);
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, b, alpha, out, n);
+    return sei_launch_status();
+}
+
+extern "C" int sei_axpy_sqrt_dev(const float *a, const float *b, const float *p, float *out, size_t n, void *stream) {
+    SEI_REQUIRE(a && b && p && out && n > 0);
+    SEI_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0 && ((uintptr_t)p & 3) == 0);
+    size_t grid = sei_ceil_div(n / 4 + 1, 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(axpy_sqrt_dev_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, b, p, out, n);
     return sei_launch_status();
 }
 
@@ -229,6 +307,27 @@ extern "C" int sei_sure_loss(const float *y, const float *y1, const float *y2, c
     fc.coef[0] = c_div; fc.coef[1] = c_mse; fc.bias = -cst;
     hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(RED_THREADS), 0, (hipStream_t)stream, (const float *)work, grid, 2,
                        fc, out3);
+    return sei_launch_status();
+}
+
+// sei_sure_loss with the multiplier eta = state[0] in device memory in the place of sigma^2, and its ascent step (UNSURE).
+extern "C" int sei_sure_loss_unsure(const float *y, const float *y1, const float *y2, const float *b, int planes, int H,
+                                    int W, int margin_div, int margin_mse, float tau, float c_mse, float inv_n_div,
+                                    float step_size, float momentum, int update, float *state, float *out3, float *g1,
+                                    float *g2, float *work, void *stream) {
+    SEI_REQUIRE(y && y1 && y2 && b && out3 && g1 && g2 && work);
+    SEI_REQUIRE(planes > 0 && H > 0 && W > 0 && margin_div >= 0 && margin_mse >= 0 && tau != 0.f);
+    SEI_REQUIRE(2 * margin_div < H && 2 * margin_div < W && 2 * margin_mse < H && 2 * margin_mse < W);
+    SEI_REQUIRE(state && ((uintptr_t)state & 15) == 0);
+    SEI_REQUIRE(momentum >= 0.f && momentum < 1.f && std::isfinite(step_size) && (update == 0 || update == 1));
+    const size_t total = (size_t)planes * H * W;
+    const int grid = reduce_blocks(total);
+    hipLaunchKernelGGL(sure_terms_unsure_kernel, dim3(grid), dim3(RED_THREADS), 0, (hipStream_t)stream, y, y1, y2, b,
+                       total, H, W, margin_div, margin_mse, 1.0f / tau, c_mse, inv_n_div, (const float *)state, g1, g2, work);
+    UnsureStep u;
+    u.c_mse = c_mse; u.inv_n_div = inv_n_div; u.step_size = step_size; u.momentum = momentum; u.update = update;
+    hipLaunchKernelGGL(finish_unsure_kernel, dim3(1), dim3(RED_THREADS), 0, (hipStream_t)stream, (const float *)work, grid,
+                       u, state, out3);
     return sei_launch_status();
 }
 

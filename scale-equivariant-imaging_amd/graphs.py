@@ -91,6 +91,9 @@ class GraphedLossStep:
         self._unit_grad = torch.ones((), dtype=torch.float32, device=device)
         from models import _ops
         self._ops = _ops
+        # State that the step itself moves in device memory (the UNSURE multiplier, losses/sure.py's `noise_state`): the
+        # warm-up steps on a zero measurement must not count. Restored IN PLACE below: the graph holds the address.
+        stepped = [(buf, buf.clone()) for name, buf in loss_module.named_buffers() if name.endswith("noise_state")]
         side = self._warm_up(warmup, device)
         # The captured step rebuilds the TRANSPOSED bf16 weight shadows from the plain bf16 copy, which
         # the fused Adam refreshes every step; make that copy current now, and re-check before each replay.
@@ -116,6 +119,8 @@ class GraphedLossStep:
             _ops.set_weight_grad_milestone(None, None, owner=backbone)
             _ops.set_fused_adam(None, None, owner=backbone)
             _ops.set_direct_bf16_grads(None, owner=backbone)
+            for buf, before in stepped:
+                buf.copy_(before)
         backbone.zero_grad_flat()
 
     def _fwd_bwd(self):

@@ -25,6 +25,28 @@ from .r2r import R2REILoss
 from .sure import SureGaussianLoss, draw_probe
 
 
+UNSURE_FLAG = "--sure_unknown_noise"
+
+
+def check_unsure_args(args, world=1):
+    """What --sure_unknown_noise cannot be combined with, refused by the flag's name before any GPU object exists
+    (`get_loss` and train.py call this; a namespace without the attribute has the flag off)."""
+    if not getattr(args, "sure_unknown_noise", False):
+        return
+    if args.method not in ("proposed", "sure"):
+        raise ValueError(f"{UNSURE_FLAG} estimates the noise level inside the SURE term: --method {args.method} has none "
+                         "(use --method proposed or --method sure)")
+    if args.method == "proposed" and getattr(args, "ProposedLoss__sure_alternative", None) == "r2r":
+        raise ValueError(f"{UNSURE_FLAG} estimates the noise level inside the SURE term, which "
+                         "--ProposedLoss__sure_alternative r2r replaces: R2R needs the level itself")
+    if world > 1:
+        raise ValueError(f"{UNSURE_FLAG} runs on one GPU: each of {world} ranks would ascend on its own divergence (the "
+                         "estimate is not all-reduced before the update)")
+    momentum = getattr(args, "unsure_momentum", 0.9)
+    if not 0.0 <= momentum < 1.0:
+        raise ValueError(f"--unsure_momentum must lie in [0, 1) with {UNSURE_FLAG}, got {momentum}")
+
+
 def _stochastic_depth_masks(model, batch):
     """The per-sample stochastic-depth masks of one model call (SwinIR in training mode), else None."""
     if model is None:
@@ -101,9 +123,11 @@ class Noise2InverseLoss(_ModelPlusOneLoss):
 
 
 class SURELoss(_ModelPlusOneLoss):
-    def __init__(self, noise_level, cropped_div, averaged_cst, margin, physics):
+    def __init__(self, noise_level, cropped_div, averaged_cst, margin, physics, unsure=False, unsure_step_size=1e-4,
+                 unsure_momentum=0.9):
         super().__init__(physics, SureGaussianLoss(sigma=noise_level / 255, cropped_div=cropped_div,
-                                                   averaged_cst=averaged_cst, margin=margin))
+                                                   averaged_cst=averaged_cst, margin=margin, unsure=unsure,
+                                                   step_size=unsure_step_size, momentum=unsure_momentum))
 
     def draw(self, y, model=None):
         first = _stochastic_depth_masks(model, y.shape[0])                       # model(y)
@@ -159,10 +183,15 @@ class ProposedLoss(Module):
     keep_outputs = False        # diagnostics: keep the restored images of the (fused) first pass in `self.kept`
 
     def __init__(self, blueprint, sure_alternative, noise_level, stop_gradient, sure_cropped_div,
-                 sure_averaged_cst, sure_margin, alpha_tradeoff, transforms, physics, fuse_passes=None):
+                 sure_averaged_cst, sure_margin, alpha_tradeoff, transforms, physics, fuse_passes=None, unsure=False,
+                 unsure_step_size=1e-4, unsure_momentum=0.9):
+        """unsure: the SURE term estimates the noise level (SureGaussianLoss(unsure=True)); it runs before the EI term in
+        both pass orders, and the EI branch's measurement noise takes the level as the SURE term left it this step."""
         super().__init__()
         self.physics = physics
         self.graph_safe = False
+        if unsure and sure_alternative == "r2r":
+            raise ValueError(f"unsure ({UNSURE_FLAG}) has no SURE term to work in under sure_alternative='r2r'")
         if transforms == "Scaling_Transforms":
             ei_transform = ScalingTransform(**blueprint[ScalingTransform.__name__])
         elif transforms == "Shifts":
@@ -181,7 +210,8 @@ class ProposedLoss(Module):
             self.fuse_passes = False
             return
         self.sure = SureGaussianLoss(sigma=noise_level / 255, cropped_div=sure_cropped_div,
-                                     averaged_cst=sure_averaged_cst, margin=sure_margin)
+                                     averaged_cst=sure_averaged_cst, margin=sure_margin, unsure=unsure,
+                                     step_size=unsure_step_size, momentum=unsure_momentum)
         self.ei = EILoss(metric=mse(), transform=ei_transform, no_grad=stop_gradient, weight=alpha_tradeoff)
         self.loss_fns = [self.sure, self.ei]
         self.compute_x_net = True
@@ -271,6 +301,10 @@ class ProposedLoss(Module):
             draws = self.draw(y, model) if self.compute_x_net else None
         ei_kw = {} if draws is None else {"transform_params": (draws["rate"], draws["center"]),
                                           "noise": draws["noise"]}
+        if self.compute_x_net and self.sure.unsure:
+            # the estimated level, read from device memory when the EI term's noise kernel runs: after the SURE term's
+            # update of this step in both pass orders below (self.loss_fns lists the SURE term first)
+            ei_kw["noise_sigma2"] = self.sure.noise_state
         drop = draws.get("drop") if draws is not None else None
         calls = [model] * 3 if drop is None else [_with_masks(model, m) for m in drop]
         if not self.fuse_passes:
@@ -307,8 +341,11 @@ class ProposedLoss(Module):
 
 class Loss(Module):
     def __init__(self, physics, blueprint, noise_level, sure_cropped_div, sure_averaged_cst, sure_margin,
-                 method, crop_training_pairs, crop_size):
+                 method, crop_training_pairs, crop_size, unsure=False, unsure_step_size=1e-4, unsure_momentum=0.9):
         super().__init__()
+        if unsure and method not in ("proposed", "sure"):
+            raise ValueError(f"unsure ({UNSURE_FLAG}) needs a SURE term: method {method!r} has none")
+        unsure_kw = dict(unsure=unsure, unsure_step_size=unsure_step_size, unsure_momentum=unsure_momentum)
         if method == "supervised":
             self.loss = SupervisedLoss(physics=physics)
         elif method == "css":
@@ -317,11 +354,11 @@ class Loss(Module):
             self.loss = Noise2InverseLoss(physics=physics)
         elif method == "sure":
             self.loss = SURELoss(physics=physics, noise_level=noise_level, cropped_div=sure_cropped_div,
-                                 averaged_cst=sure_averaged_cst, margin=sure_margin)
+                                 averaged_cst=sure_averaged_cst, margin=sure_margin, **unsure_kw)
         elif method == "proposed":
             self.loss = ProposedLoss(physics=physics, blueprint=blueprint, noise_level=noise_level,
                                      sure_cropped_div=sure_cropped_div, sure_averaged_cst=sure_averaged_cst,
-                                     sure_margin=sure_margin, **blueprint[ProposedLoss.__name__])
+                                     sure_margin=sure_margin, **blueprint[ProposedLoss.__name__], **unsure_kw)
         else:
             raise ValueError(f"Unknwon method: {method}")
 
@@ -332,6 +369,11 @@ class Loss(Module):
             self.crop_fn = None
         if "HOMOGENEOUS_SWINIR" in environ:
             self.crop_fn = None
+
+    def unsure_term(self):
+        """The SURE term that estimates the noise level (it owns `noise_state` and `estimated_sigma`), or None."""
+        term = getattr(self.loss, "sure", None) or getattr(self.loss, "loss", None)
+        return term if isinstance(term, SureGaussianLoss) and term.unsure else None
 
     def forward(self, x, y, model, draws=None):
         """draws: the step's device-side random numbers (`self.loss.draw(y_cropped)`), injected by tests and by
@@ -344,6 +386,7 @@ class Loss(Module):
 
 
 def get_loss(args, physics):
+    check_unsure_args(args)
     if args.partial_sure:
         if args.sure_margin is not None:
             sure_margin = args.sure_margin
@@ -377,6 +420,12 @@ def get_loss(args, physics):
             "antialias": args.ScalingTransform__antialias,
         },
     }
-    return Loss(physics=physics, blueprint=blueprint, method=args.method, noise_level=args.noise_level,
+    # (tests and bench.py build their namespaces without the UNSURE options: off, the defaults)
+    unsure = bool(getattr(args, "sure_unknown_noise", False))
+    noise_level = args.noise_level
+    if unsure and getattr(args, "unsure_init_noise_level", None) is not None:
+        noise_level = args.unsure_init_noise_level           # the starting guess; the measurements keep --noise_level
+    return Loss(physics=physics, blueprint=blueprint, method=args.method, noise_level=noise_level,
                 sure_cropped_div=args.sure_cropped_div, sure_averaged_cst=args.sure_averaged_cst,
-                sure_margin=sure_margin, **blueprint[Loss.__name__])
+                sure_margin=sure_margin, unsure=unsure, unsure_step_size=getattr(args, "unsure_step_size", 1e-4),
+                unsure_momentum=getattr(args, "unsure_momentum", 0.9), **blueprint[Loss.__name__])

@@ -6,12 +6,50 @@
 `cropped_div`), b ~ N(0,1) on that interior and 0 outside, cst = sigma^2 (averaged_cst) or
 sigma^2 / batch_size. The two interior reductions and both gradients come out of one fused HIP kernel
 (`sei_sure_terms`); the probe y + tau*b is `sei_axpy`.
+
+`SureGaussianLoss(unsure=True)` is the same term for an UNKNOWN noise level (UNSURE; restated from the paper, see the
+constructor): sigma^2 becomes a multiplier in device memory that `sei_sure_loss_unsure` reads and moves by gradient ascent.
 """
 import torch
 import torch.nn as nn
 
 import _native as N
 from physics._ops import axpy
+
+
+def _terms_buffers(ctx, y, y1, y2, b, margin_div, margin_mse):
+    """What both SURE entry points take: the operands checked, the outputs and the gradients allocated and saved on `ctx`.
+    -> (n_div, n_mse, out3, work, (y1, y2, g1, g2 pointers))."""
+    joint = y2 is None
+    B, C, H, W = y.shape
+    for name, t in (("y", y), ("y1", y1), ("b", b)) + (() if joint else (("y2", y2),)):
+        N.check_tensor(t, name)
+        if t.shape != ((2 * B, C, H, W) if joint and name == "y1" else y.shape):
+            raise ValueError("SURE: y, A(x_net), A(f(y + tau b)) and b must share one shape")
+    n_div = B * C * (H - 2 * margin_div) * (W - 2 * margin_div)
+    n_mse = B * C * (H - 2 * margin_mse) * (W - 2 * margin_mse)
+    out = torch.empty(3, dtype=torch.float32, device=y.device)
+    work = torch.empty(2 * N.SEI_REDUCE_BLOCKS, dtype=torch.float32, device=y.device)
+    if joint:
+        g = torch.empty_like(y1)
+        half = y.numel() * y.element_size()
+        ptrs = (y1.data_ptr(), y1.data_ptr() + half, g.data_ptr(), g.data_ptr() + half)
+        ctx.save_for_backward(g)
+    else:
+        g1, g2 = torch.empty_like(y), torch.empty_like(y)
+        ptrs = (y1.data_ptr(), y2.data_ptr(), g1.data_ptr(), g2.data_ptr())
+        ctx.save_for_backward(g1, g2)
+    ctx.joint = joint
+    return n_div, n_mse, out, work, ptrs
+
+
+def _scaled_terms_grads(ctx, go, nargs):
+    """The saved gradients times the incoming one, in the places of y1 (and y2) among `nargs` forward arguments."""
+    if ctx.joint:
+        (g,) = ctx.saved_tensors
+        return (None, N.scale_by(g, go)) + (None,) * (nargs - 2)
+    g1, g2 = ctx.saved_tensors
+    return (None, N.scale_by(g1, go), N.scale_by(g2, go)) + (None,) * (nargs - 3)
 
 
 class _SureTerms(torch.autograd.Function):
@@ -21,38 +59,38 @@ class _SureTerms(torch.autograd.Function):
         model outputs at once): its halves are read in place and one gradient tensor comes back for it -- autograd then has
         no slices to differentiate (two zero fills, two copies and an add per step). The loss value
         c_mse * mse_sum + c_div * div_sum - cst is formed by the kernel's own last stage (sei_sure_loss)."""
-        joint = y2 is None
         B, C, H, W = y.shape
-        for name, t in (("y", y), ("y1", y1), ("b", b)) + (() if joint else (("y2", y2),)):
-            N.check_tensor(t, name)
-            if t.shape != ((2 * B, C, H, W) if joint and name == "y1" else y.shape):
-                raise ValueError("SURE: y, A(x_net), A(f(y + tau b)) and b must share one shape")
-        n_div = B * C * (H - 2 * margin_div) * (W - 2 * margin_div)
-        n_mse = B * C * (H - 2 * margin_mse) * (W - 2 * margin_mse)
+        n_div, n_mse, out, work, ptrs = _terms_buffers(ctx, y, y1, y2, b, margin_div, margin_mse)
         c_mse, c_div = 1.0 / n_mse, 2.0 * sigma2 / n_div
-        out = torch.empty(3, dtype=torch.float32, device=y.device)
-        work = torch.empty(2 * N.SEI_REDUCE_BLOCKS, dtype=torch.float32, device=y.device)
-        if joint:
-            g = torch.empty_like(y1)
-            half = y.numel() * y.element_size()
-            ptrs = (y1.data_ptr(), y1.data_ptr() + half, g.data_ptr(), g.data_ptr() + half)
-            ctx.save_for_backward(g)
-        else:
-            g1, g2 = torch.empty_like(y), torch.empty_like(y)
-            ptrs = (y1.data_ptr(), y2.data_ptr(), g1.data_ptr(), g2.data_ptr())
-            ctx.save_for_backward(g1, g2)
-        ctx.joint = joint
         N.call("sei_sure_loss", y.data_ptr(), ptrs[0], ptrs[1], b.data_ptr(), B * C, H, W, margin_div, margin_mse, tau,
                c_mse, c_div, float(cst), out.data_ptr(), ptrs[2], ptrs[3], work.data_ptr())
         return out[2]
 
     @staticmethod
     def backward(ctx, go):
-        if ctx.joint:
-            (g,) = ctx.saved_tensors
-            return (None, N.scale_by(g, go)) + (None,) * 7
-        g1, g2 = ctx.saved_tensors
-        return (None, N.scale_by(g1, go), N.scale_by(g2, go)) + (None,) * 6
+        return _scaled_terms_grads(ctx, go, 9)
+
+
+class _UnsureTerms(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, y1, y2, b, margin_div, margin_mse, tau, state, step_size, momentum, update):
+        """_SureTerms with the multiplier eta = state[0] in device memory in the place of sigma^2 (sei_sure_loss_unsure):
+        loss = c_mse * mse_sum + 2 eta * div_sum / n_div, the gradients carry eta as it stands on entry, and with `update`
+        the kernel's last stage then moves `state` = {eta, m, k, unused} one ascent step, in place. No gradient reaches
+        `state`: the multiplier is not a parameter of the descent."""
+        B, C, H, W = y.shape
+        N.check_tensor(state, "noise_state")
+        if state.numel() != 4 or state.device != y.device:
+            raise ValueError("UNSURE: noise_state must hold four floats on the device of y (move the loss module there)")
+        n_div, n_mse, out, work, ptrs = _terms_buffers(ctx, y, y1, y2, b, margin_div, margin_mse)
+        N.call("sei_sure_loss_unsure", y.data_ptr(), ptrs[0], ptrs[1], b.data_ptr(), B * C, H, W, margin_div, margin_mse,
+               tau, 1.0 / n_mse, 1.0 / n_div, float(step_size), float(momentum), int(bool(update)), state.data_ptr(),
+               out.data_ptr(), ptrs[2], ptrs[3], work.data_ptr())
+        return out[2]
+
+    @staticmethod
+    def backward(ctx, go):
+        return _scaled_terms_grads(ctx, go, 11)
 
 
 def draw_probe(y, margin):
@@ -75,7 +113,17 @@ def embed_probe(y, b_interior, margin):
 
 
 class SureGaussianLoss(nn.Module):
-    def __init__(self, sigma, tau=1e-2, margin=0, cropped_div=False, averaged_cst=False):
+    def __init__(self, sigma, tau=1e-2, margin=0, cropped_div=False, averaged_cst=False, unsure=False, step_size=1e-4,
+                 momentum=0.9):
+        """unsure: the noise level is unknown (UNSURE, Tachella, Davies, Jacques; restated from the paper -- deepinv is
+        not part of this tree, parity with its SureGaussianLoss(unsure=True) is unpinned). sigma^2 becomes a Lagrange
+        multiplier eta that starts at `sigma`^2 and takes one step of gradient ascent per training-mode forward:
+
+            loss = mean_int((A(x_net) - y)^2) + 2 eta d,   d = mean_int(b * (A(f(y + tau b)) - A(x_net)) / tau)
+            g = 2 d;  m' = g on the first step, else momentum * m + (1 - momentum) * g;  eta' = eta + step_size * m'
+
+        (no constant term; the update uses the averaged direction m'). The state {eta, m, k, unused} is the float32
+        buffer `noise_state`: the kernels read and write it in device memory, so a captured step replays the update."""
         super().__init__()
         self.name = "SureGaussian"
         self.sigma2 = sigma**2
@@ -84,10 +132,29 @@ class SureGaussianLoss(nn.Module):
         self.margin = margin
         self.cropped_div = cropped_div
         self.averaged_cst = averaged_cst
+        self.unsure = bool(unsure)
+        if self.unsure:
+            if not 0.0 <= momentum < 1.0:
+                raise ValueError(f"UNSURE: momentum must lie in [0, 1), got {momentum}")
+            self.step_size, self.momentum = float(step_size), float(momentum)
+            self.register_buffer("noise_state", torch.tensor([self.sigma2, 0.0, 0.0, 0.0], dtype=torch.float32))
 
     @property
     def div_margin(self):
         return self.margin if self.cropped_div else 0
+
+    def estimated_sigma(self):
+        """sqrt(max(eta, 0)) as a host float: a synchronisation, for use outside the step only."""
+        if not self.unsure:
+            raise RuntimeError("estimated_sigma: this SURE term was built with a known noise level (unsure=False)")
+        return max(float(self.noise_state[0]), 0.0) ** 0.5
+
+    def _terms(self, y, y1, y2, b):
+        if self.unsure:
+            return _UnsureTerms.apply(y, y1, y2, b, self.div_margin, self.margin, self.tau, self.noise_state,
+                                      self.step_size, self.momentum, self.training)
+        cst = self.sigma2 if self.averaged_cst else self.sigma2 / y.size(0)
+        return _SureTerms.apply(y, y1, y2, b, self.div_margin, self.margin, self.tau, self.sigma2, cst)
 
     def forward(self, y, x_net, physics, model, b=None, y1=None, y2=None, y12=None, **kwargs):
         """`b` (full-size probe), `y1` = A(x_net) and `y2` = A(model(y + tau b)) may be supplied by a
@@ -96,16 +163,14 @@ class SureGaussianLoss(nn.Module):
         y = y.contiguous()
         if b is None:
             b = draw_probe(y, self.div_margin)
-        cst = self.sigma2 if self.averaged_cst else self.sigma2 / y.size(0)
         if y12 is not None:
-            loss = _SureTerms.apply(y, y12.contiguous(), None, b, self.div_margin, self.margin, self.tau, self.sigma2, cst)
+            loss = self._terms(y, y12.contiguous(), None, b)
         else:
             if y1 is None:
                 y1 = physics.A(x_net)
             if y2 is None:
                 y2 = physics.A(model(axpy(y, b, self.tau)))
-            loss = _SureTerms.apply(y, y1.contiguous(), y2.contiguous(), b, self.div_margin, self.margin, self.tau,
-                                    self.sigma2, cst)
+            loss = self._terms(y, y1.contiguous(), y2.contiguous(), b)
         from os import environ
         if "_TEMPORARY_HOTFIX" in environ:       # reference :68-74
             assert physics.rate is not None

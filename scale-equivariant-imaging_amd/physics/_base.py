@@ -4,7 +4,7 @@ documented behaviour -- SURVEY.md a6, 8c)."""
 import torch
 from torch.nn import Module
 
-from ._ops import axpy
+from ._ops import axpy, axpy_sqrt_dev
 
 
 class GaussianNoise(Module):
@@ -14,9 +14,13 @@ class GaussianNoise(Module):
         super().__init__()
         self.sigma = sigma
 
-    def forward(self, x, noise=None):
+    def forward(self, x, noise=None, noise_sigma2=None):
+        """noise_sigma2: a float32 device tensor whose first element stands for sigma^2 in the place of `self.sigma`
+        (negative: no noise); the kernel reads it from device memory, so a captured step follows a level that moves."""
         if noise is None:
             noise = torch.randn_like(x)
+        if noise_sigma2 is not None:
+            return axpy_sqrt_dev(x.contiguous(), noise.contiguous(), noise_sigma2)
         return axpy(x.contiguous(), noise.contiguous(), self.sigma)
 
 

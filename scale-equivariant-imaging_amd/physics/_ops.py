@@ -279,3 +279,32 @@ class _Axpy(torch.autograd.Function):
 def axpy(a, b, alpha):
     """a + alpha*b (measurement noise, SURE probe)."""
     return _Axpy.apply(a, b, float(alpha))
+
+
+class _AxpySqrtDev(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, sigma2):
+        N.check_tensor(a, "a")
+        N.check_tensor(b, "b")
+        N.check_tensor(sigma2, "sigma2")
+        if a.shape != b.shape:
+            raise ValueError("axpy: shape mismatch")
+        if sigma2.numel() < 1 or sigma2.device != a.device:
+            raise ValueError("axpy: sigma2 must be a float32 tensor on the device of the operands")
+        ctx.sigma2 = sigma2
+        a, b = (t if N.aligned(t) else t.clone() for t in (a, b))       # (as _Axpy: float4 reads and writes)
+        out = torch.empty_like(a)
+        N.call("sei_axpy_sqrt_dev", a.data_ptr(), b.data_ptr(), sigma2.data_ptr(), out.data_ptr(), a.numel())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        # (the level as it stands now: between forward and backward of one step nothing moves it)
+        gb = g * ctx.sigma2.reshape(-1)[0].clamp_min(0).sqrt() if ctx.needs_input_grad[1] else None
+        return g, gb, None
+
+
+def axpy_sqrt_dev(a, b, sigma2):
+    """a + sqrt(max(sigma2[0], 0)) * b with `sigma2` read from device memory by the kernel (measurement noise at a level
+    that a captured step moves: losses/sure.py's `noise_state`). No gradient reaches `sigma2`."""
+    return _AxpySqrtDev.apply(a, b, sigma2)

@@ -5,13 +5,17 @@ import os
 import torch
 
 
-def save_training_state(epoch, model, optimizer, scheduler, state_path):
+def save_training_state(epoch, model, optimizer, scheduler, state_path, loss_state=None):
+    """loss_state: what the loss itself learns (the UNSURE noise estimate, train.py --sure_unknown_noise), stored under
+    the key "loss_state"; None leaves the file as the reference writes it."""
     folder = os.path.dirname(state_path)
     if folder:
         os.makedirs(folder, exist_ok=True)
     print(f"writing the training state to the file {state_path}")
     state = {"epoch": epoch, "params": model.get_weights(), "optimizer": optimizer.state_dict(),
              "scheduler": scheduler.state_dict()}
+    if loss_state is not None:
+        state["loss_state"] = loss_state
     torch.save(state, state_path)
 
 

@@ -27,6 +27,11 @@ step runs in libsei_hip.so. Differences, all build-side and documented in DESIGN
     literal sequence (losses/weights_distance_loss.py + torch.optim.SGD / torch.optim.Adam).
     The reference's assertions are ValueErrors raised before anything touches the GPU; `--fine_tuning_params` with the
     Convolutional architecture, which has no `conv_last`, is one of them (the reference dies in `get_parameter`).
+  * `--sure_unknown_noise` (UNSURE, restated from the paper; not in the reference): `--method proposed | sure` without a
+    known noise level. The sigma^2 of the SURE term is a multiplier in device memory, started from
+    `--unsure_init_noise_level` (default `--noise_level`) and moved by the loss kernel itself every step
+    (`--unsure_step_size`, `--unsure_momentum`), so the step still replays from a hipGraph; the csv gets a third column
+    `Estimated Noise Level` and the checkpoints a key `loss_state`, which `--RESUME` restores. One GPU.
 """
 import csv
 import os
@@ -45,7 +50,7 @@ import crop  # noqa: E402
 import graphs  # noqa: E402
 import parallel  # noqa: E402
 from datasets import get_dataset  # noqa: E402
-from losses import get_loss  # noqa: E402
+from losses import check_unsure_args, get_loss  # noqa: E402
 from models import get_model  # noqa: E402
 from optim import FlatAdam, FlatSGD  # noqa: E402
 from physics import get_physics  # noqa: E402
@@ -107,6 +112,15 @@ def build_parser():
               "this rank's 1 / world share and the UPDATED weights are all-gathered (sharded optimizer step; with another "
               "optimizer: reduce-scatter + all-gather of the gradients); all_reduce = chunked all-reduce, every rank "
               "steps the whole bucket (parallel.py, optim.py)")
+    flag("--sure_unknown_noise", default=False, **onoff,
+         help="UNSURE: --method proposed | sure without a known noise level. The sigma^2 in front of the SURE divergence "
+              "becomes a multiplier in device memory that the loss kernel moves by gradient ascent every step; the csv "
+              "gets a third column with the estimate (one GPU)")
+    flag("--unsure_step_size", type=float, default=1e-4, help="ascent step of the multiplier (--sure_unknown_noise)")
+    flag("--unsure_momentum", type=float, default=0.9, help="averaging of the ascent direction, in [0, 1)")
+    flag("--unsure_init_noise_level", type=float, default=None,
+         help="starting guess of the noise level on --noise_level's 0..255 scale (default: --noise_level, which keeps "
+              "generating the synthetic measurements)")
     flag("--device_cache", default=False, **onoff,
          help="keep every (x, y) training pair in HBM (deterministic measurements) and draw crops on the device "
               "instead of the per-item DataLoader path (datasets/device_cache.py)")
@@ -173,6 +187,7 @@ def main(argv=None):
         args.device = f"cuda:{local_rank % torch.cuda.device_count()}"     # (% only matters for shared-GPU rehearsals)
         torch.cuda.set_device(args.device)
     check_fine_tuning_args(args)
+    check_unsure_args(args, world)
     crop.FIX_BATCHED_CROP = args.fix_batched_crop
 
     physics = get_physics(args, device=args.device)
@@ -187,6 +202,9 @@ def main(argv=None):
     torch.cuda.manual_seed(seed)                      # decorrelated b / noise / rates / centres per rank
 
     loss = get_loss(args=args, physics=physics)
+    unsure = loss.unsure_term()                       # the SURE term that owns the estimated noise level, or None
+    if unsure is not None:
+        unsure.to(args.device)
     if isdir(args.dataset):
         dataset = measurement_folder(args.dataset, args.PrepareTrainingPairs__crop_size, args.device)
     else:
@@ -266,7 +284,7 @@ def main(argv=None):
         os.makedirs(args.out_dir, exist_ok=True)
         file = open(f"{args.out_dir}/training.csv", "w", newline="", buffering=1)
         log = csv.writer(file)
-        log.writerow(["Epoch", "Training Loss"])
+        log.writerow(["Epoch", "Training Loss"] + (["Estimated Noise Level"] if unsure is not None else []))
 
     scheduler_disabled = False
     if args.RESUME is not None:
@@ -281,6 +299,16 @@ def main(argv=None):
             group["lr"] = args.lr
         if getattr(optimizer, "anchor", None) is not None:    # FlatSGD / FlatAdam with the penalty folded in
             optimizer.anchor.copy_(backbone.flat_params)      # as upstream: the penalty's anchor is the resumed model
+        if unsure is not None:
+            if "loss_state" not in ckp:
+                raise ValueError(f"--sure_unknown_noise: {args.RESUME} holds no loss_state (it was written without the flag)")
+            unsure.load_state_dict(ckp["loss_state"])         # in place: a captured step reads the buffer's address
+    if unsure is not None and os.environ.get("SEI_TRACE_UNSURE_STATE") == "1" and rank == 0:
+        eta, m, k = unsure.noise_state[:3].tolist()           # tests: what the first step starts from
+        print(f"unsure state at start: eta {eta!r} m {m!r} k {k!r}")
+
+    def loss_state():
+        return None if unsure is None else unsure.state_dict()
 
     checkpoints_dir = f"{args.out_dir}/checkpoints"
 
@@ -296,7 +324,7 @@ def main(argv=None):
     consolidate()
     if rank == 0:
         save_training_state(epoch=0, model=model, optimizer=optimizer, scheduler=scheduler,
-                            state_path=checkpoint_name(0))
+                            state_path=checkpoint_name(0), loss_state=loss_state())
 
     # the reference's literal penalty (a deepcopy of the model as it stands here, added to the loss before backward()):
     # every optimizer but FlatSGD and the fine-tuning FlatAdam, whose kernels apply the same penalty and leave its value in
@@ -369,10 +397,17 @@ def main(argv=None):
             consolidate()
         if rank == 0:
             stamp = datetime.now().strftime("%Y-%m-%d %H:%M:%S")
-            print(f"\t{stamp}\t[{epoch + 1:{len(str(int(epochs)))}d}/{epochs}]\tTraining_Loss: {epoch_loss:.2e}")
-            log.writerow([epoch + 1, epoch_loss])
+            line = f"\t{stamp}\t[{epoch + 1:{len(str(int(epochs)))}d}/{epochs}]\tTraining_Loss: {epoch_loss:.2e}"
+            row = [epoch + 1, epoch_loss]
+            if unsure is not None:
+                estimate = 255 * unsure.estimated_sigma()     # (a sync, once per epoch and outside the step)
+                line += f"\tEstimated_Noise_Level: {estimate:.3f}"
+                row.append(estimate)
+            print(line)
+            log.writerow(row)
             if (epoch % checkpoint_interval == 0) or (epoch == epochs - 1):
-                save_training_state(epoch, model, optimizer, scheduler, checkpoint_name(epoch + 1))
+                save_training_state(epoch, model, optimizer, scheduler, checkpoint_name(epoch + 1),
+                                    loss_state=loss_state())
 
     if rank == 0:
         torch.save(model.get_weights(), f"{args.out_dir}/weights.pt")
