@@ -274,6 +274,26 @@ int sei_sure_loss_unsure(const float *y, const float *y1, const float *y2, const
                          float momentum, int update, float *state, float *out3, float *g1, float *g2, float *work,
                          void *stream);
 int sei_axpy_sqrt_dev(const float *a, const float *b, const float *p, float *out, size_t n, void *stream);
+/* Poisson-Gaussian UNSURE (the same paper's signal-dependent case; restated from it): the noise variance at a pixel is
+ * sigma^2 + gain * (clean value) with BOTH levels unknown, so the single multiplier becomes the affine weight eta + gamma y_i
+ * inside the divergence, with one multiplier per zero-expected-divergence constraint. sei_sure_loss_unsure's two launches
+ * with a third partial sum. state = {eta, m_eta, k, 0, gamma, m_gamma, 0, 0} (16-byte aligned; slots 0..2 as above).
+ *   stage 1   D0 = sum_int_d b (y2 - y1) inv_tau, D1 = sum_int_d y b (y2 - y1) inv_tau, the mse sum; the gradients with
+ *             the multipliers as they stood on entry: g2_i = ((2 w_i) inv_n_div) b_i inv_tau, w_i = fmaf(gamma, y_i, eta),
+ *             g1_i = 2 c_mse (y1 - y)_i - g2_i, zero outside the respective interiors. y1 / y2 and g1 / g2 may be the
+ *             halves of one 2B-image tensor. `work` holds 3 * SEI_REDUCE_BLOCKS floats.
+ *   stage 2   out4 = {D0, D1, mse sum, c_mse out4[2] + 2 (eta d0 + gamma d1)}, d = D inv_n_div; then, if `update`, the
+ *             ascent step above for each multiplier: eta along g = 2 d0 by step_eta, gamma along g = 2 d1 by step_gamma, one
+ *             shared momentum, k' = k + 1 once. Neither multiplier is clamped. With update == 0 the state is not written.
+ * With gamma == 0 (and step_gamma == 0) out4[0], out4[2], out4[3], g1, g2 and state[0..2] are sei_sure_loss_unsure's bits.
+ * Refused: what sei_sure_loss_unsure refuses, and a non-finite step_gamma.
+ * sei_axpy_hetero_dev: out_i = a_i + sqrt(max(fmaf(state[4], a_i, state[0]), 0)) b_i (the measurement noise of the equivariant
+ * branch at the estimated, signal-dependent level); sei_axpy's float4 body, tail and alignment. */
+int sei_sure_loss_unsure_pg(const float *y, const float *y1, const float *y2, const float *b, int planes, int H, int W,
+                            int margin_div, int margin_mse, float tau, float c_mse, float inv_n_div, float step_eta,
+                            float step_gamma, float momentum, int update, float *state, float *out4, float *g1, float *g2,
+                            float *work, void *stream);
+int sei_axpy_hetero_dev(const float *a, const float *b, const float *state, float *out, size_t n, void *stream);
 /* Numerator of the luma PSNR of the evaluation step (reference src/metrics.py:10-13: kornia rgb_to_ycbcr's
  * Y = 0.299 R + 0.587 G + 0.114 B, torchmetrics PSNR with data_range 1): out1[0] = sum over the npix pixels of
  * (Y(a) - Y(b))^2 for planar RGB images a, b of shape (3, npix). `work` holds SEI_REDUCE_BLOCKS floats. */

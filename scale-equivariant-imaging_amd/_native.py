@@ -53,6 +53,8 @@ SIGNATURES = {
     "sei_mse_loss": [_P, _P, _Z, _F, _F, _P, _P, _P, _P],
     "sei_sure_loss_unsure": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P],
     "sei_axpy_sqrt_dev": [_P, _P, _P, _P, _Z, _P],
+    "sei_sure_loss_unsure_pg": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P],
+    "sei_axpy_hetero_dev": [_P, _P, _P, _P, _Z, _P],
     "sei_luma_sqerr": [_P, _P, _Z, _P, _P, _P],
     "sei_ssim_luma": [_P, _P, _I, _I, _I, _P, _P, _P],
     "sei_lpips_conv_relu": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],

@@ -9,6 +9,10 @@
 //                    step (UNSURE, Tachella, Davies, Jacques; restated from the paper, no reference lines: the reference's
 //                    sure.py predates it)
 //   sei_axpy_sqrt_dev : y + sqrt(max(eta, 0))*n, deepinv GaussianNoise with the multiplier read from device memory
+//   sei_sure_loss_unsure_pg : the same for Poisson-Gaussian noise (variance sigma^2 + gain * signal) with both levels unknown:
+//                    the weight in front of the divergence is eta + gamma y per pixel, two multipliers with one ascent step
+//                    each (Poisson-Gaussian UNSURE, the same paper; restated from it, no reference lines)
+//   sei_axpy_hetero_dev : y + sqrt(max(eta + gamma y, 0))*n, the noise of that model at the two multipliers in device memory
 #include <cmath>
 
 #include "sei_common.h"
@@ -17,7 +21,19 @@ namespace {
 
 constexpr int RED_THREADS = 256;
 
-__device__ __forceinline__ void axpy_body(const float *__restrict__ a, const float *__restrict__ b, float alpha,
+// out = a + alpha(a) b. The factor of b: one value for the whole launch (ConstAlpha), or the Poisson-Gaussian standard
+// deviation at the signal a, sqrt(max(eta + gamma a, 0)) (HeteroAlpha).
+struct ConstAlpha {
+    float alpha;
+    __device__ __forceinline__ float operator()(float) const { return alpha; }
+};
+struct HeteroAlpha {
+    float eta, gamma;
+    __device__ __forceinline__ float operator()(float a) const { return sqrtf(fmaxf(fmaf(gamma, a, eta), 0.f)); }
+};
+
+template <class Alpha>
+__device__ __forceinline__ void axpy_body(const float *__restrict__ a, const float *__restrict__ b, Alpha alpha,
                                           float *__restrict__ out, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t n4 = n / 4;
@@ -26,31 +42,57 @@ __device__ __forceinline__ void axpy_body(const float *__restrict__ a, const flo
     float4 *o4 = reinterpret_cast<float4 *>(out);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 va = a4[i], vb = b4[i];
-        o4[i] = make_float4(fmaf(alpha, vb.x, va.x), fmaf(alpha, vb.y, va.y), fmaf(alpha, vb.z, va.z),
-                            fmaf(alpha, vb.w, va.w));
+        o4[i] = make_float4(fmaf(alpha(va.x), vb.x, va.x), fmaf(alpha(va.y), vb.y, va.y), fmaf(alpha(va.z), vb.z, va.z),
+                            fmaf(alpha(va.w), vb.w, va.w));
     }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        out[i] = fmaf(alpha, b[i], a[i]);
+    for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float va = a[i];
+        out[i] = fmaf(alpha(va), b[i], va);
+    }
 }
 
 __global__ __launch_bounds__(256) void axpy_kernel(const float *__restrict__ a, const float *__restrict__ b,
                                                    float alpha, float *__restrict__ out, size_t n) {
-    axpy_body(a, b, alpha, out, n);
+    axpy_body(a, b, ConstAlpha{alpha}, out, n);
 }
 
 // alpha = sqrt(max(*p, 0)) read from device memory by every thread (one cached scalar load): the UNSURE noise level
 __global__ __launch_bounds__(256) void axpy_sqrt_dev_kernel(const float *__restrict__ a, const float *__restrict__ b,
                                                             const float *__restrict__ p, float *__restrict__ out,
                                                             size_t n) {
-    axpy_body(a, b, sqrtf(fmaxf(*p, 0.f)), out, n);
+    axpy_body(a, b, ConstAlpha{sqrtf(fmaxf(*p, 0.f))}, out, n);
 }
 
-// stage 1: per-block partial sums of the two SURE terms + elementwise gradients
+// alpha_i = sqrt(max(state[0] + state[4] a_i, 0)): the Poisson-Gaussian UNSURE state {eta, m_eta, k, 0, gamma, m_gamma, 0, 0}
+__global__ __launch_bounds__(256) void axpy_hetero_dev_kernel(const float *__restrict__ a, const float *__restrict__ b,
+                                                              const float *__restrict__ state, float *__restrict__ out,
+                                                              size_t n) {
+    axpy_body(a, b, HeteroAlpha{state[0], state[4]}, out, n);
+}
+
+// The coefficient of the divergence term at one pixel, 2 (noise variance) / n_div: one value for all pixels (ConstWeight:
+// a known sigma^2, or the UNSURE multiplier), or affine in the measurement (AffineWeight: Poisson-Gaussian UNSURE,
+// variance eta + gamma y; it also asks for the third sum, of y times the divergence terms). With gamma == 0 AffineWeight
+// performs ConstWeight's operations on c_div = (2 eta) inv_n_div: the same bits.
+struct ConstWeight {
+    static constexpr bool kSignal = false;
+    float c_div;
+    __device__ __forceinline__ float operator()(float) const { return c_div; }
+};
+struct AffineWeight {
+    static constexpr bool kSignal = true;
+    float eta, gamma, inv_n_div;
+    __device__ __forceinline__ float operator()(float yy) const { return (2.f * fmaf(gamma, yy, eta)) * inv_n_div; }
+};
+
+// stage 1: per-block partial sums of the two SURE terms (three with a signal-dependent weight: the partials then lie in the
+// order div, y-weighted div, mse) + elementwise gradients
+template <class Weight>
 __device__ __forceinline__ void sure_terms_body(
     const float *__restrict__ y, const float *__restrict__ y1, const float *__restrict__ y2,
     const float *__restrict__ b, size_t total, int H, int W, int md, int mm, float inv_tau, float c_mse,
-    float c_div, float *__restrict__ g1, float *__restrict__ g2, float *__restrict__ work, float *scratch) {
-    float s_div = 0.f, s_mse = 0.f;
+    Weight weight, float *__restrict__ g1, float *__restrict__ g2, float *__restrict__ work, float *scratch) {
+    float s_div = 0.f, s_mse = 0.f, s_ydiv = 0.f;
     const size_t stride = (size_t)gridDim.x * RED_THREADS;
     for (size_t i = (size_t)blockIdx.x * RED_THREADS + threadIdx.x; i < total; i += stride) {
         const int p = (int)(i % ((size_t)H * W));
@@ -61,7 +103,16 @@ __device__ __forceinline__ void sure_terms_body(
         float ga = 0.f, gb = 0.f;
         if (in_d) {
             const float bb = b[i];
-            s_div += bb * (y2[i] - v1) * inv_tau;
+            const float term = bb * (y2[i] - v1) * inv_tau;
+            s_div += term;
+            float c_div;
+            if constexpr (Weight::kSignal) {
+                const float yy = y[i];
+                s_ydiv += yy * term;
+                c_div = weight(yy);
+            } else {
+                c_div = weight(0.f);
+            }
             gb = c_div * bb * inv_tau;
             ga = -gb;
         }
@@ -75,7 +126,14 @@ __device__ __forceinline__ void sure_terms_body(
     }
     const float bd = sei_block_sum<RED_THREADS>(s_div, scratch);
     const float bm = sei_block_sum<RED_THREADS>(s_mse, scratch);
-    if (threadIdx.x == 0) {
+    if constexpr (Weight::kSignal) {
+        const float by = sei_block_sum<RED_THREADS>(s_ydiv, scratch);
+        if (threadIdx.x == 0) {
+            work[blockIdx.x] = bd;
+            work[SEI_REDUCE_BLOCKS + blockIdx.x] = by;
+            work[2 * SEI_REDUCE_BLOCKS + blockIdx.x] = bm;
+        }
+    } else if (threadIdx.x == 0) {
         work[blockIdx.x] = bd;
         work[SEI_REDUCE_BLOCKS + blockIdx.x] = bm;
     }
@@ -86,7 +144,7 @@ __global__ __launch_bounds__(RED_THREADS) void sure_terms_kernel(
     const float *__restrict__ b, size_t total, int H, int W, int md, int mm, float inv_tau, float c_mse,
     float c_div, float *__restrict__ g1, float *__restrict__ g2, float *__restrict__ work) {
     __shared__ float scratch[RED_THREADS / 64];
-    sure_terms_body(y, y1, y2, b, total, H, W, md, mm, inv_tau, c_mse, c_div, g1, g2, work, scratch);
+    sure_terms_body(y, y1, y2, b, total, H, W, md, mm, inv_tau, c_mse, ConstWeight{c_div}, g1, g2, work, scratch);
 }
 
 // stage 1 with c_div = 2 eta / n_div formed from the multiplier in device memory (state[0]; UNSURE): every workgroup reads
@@ -98,7 +156,19 @@ __global__ __launch_bounds__(RED_THREADS) void sure_terms_unsure_kernel(
     float *__restrict__ work) {
     __shared__ float scratch[RED_THREADS / 64];
     const float c_div = (2.f * state[0]) * inv_n_div;
-    sure_terms_body(y, y1, y2, b, total, H, W, md, mm, inv_tau, c_mse, c_div, g1, g2, work, scratch);
+    sure_terms_body(y, y1, y2, b, total, H, W, md, mm, inv_tau, c_mse, ConstWeight{c_div}, g1, g2, work, scratch);
+}
+
+// stage 1 with the per-pixel weight eta + gamma y formed from the two multipliers in device memory (state[0], state[4];
+// Poisson-Gaussian UNSURE), read by every workgroup before the finishing block of the same call may move them
+__global__ __launch_bounds__(RED_THREADS) void sure_terms_unsure_pg_kernel(
+    const float *__restrict__ y, const float *__restrict__ y1, const float *__restrict__ y2,
+    const float *__restrict__ b, size_t total, int H, int W, int md, int mm, float inv_tau, float c_mse,
+    float inv_n_div, const float *__restrict__ state, float *__restrict__ g1, float *__restrict__ g2,
+    float *__restrict__ work) {
+    __shared__ float scratch[RED_THREADS / 64];
+    sure_terms_body(y, y1, y2, b, total, H, W, md, mm, inv_tau, c_mse, AffineWeight{state[0], state[4], inv_n_div}, g1, g2,
+                    work, scratch);
 }
 
 __global__ __launch_bounds__(RED_THREADS) void mse_terms_kernel(const float *__restrict__ a,
@@ -198,6 +268,44 @@ __global__ __launch_bounds__(RED_THREADS) void finish_unsure_kernel(const float 
     }
 }
 
+// stage 2 of the Poisson-Gaussian UNSURE loss: three sums (div D0, y-weighted div D1, mse), loss = c_mse mse + 2 (eta d0 +
+// gamma d1) with d = D / n_div, then -- `update` -- finish_unsure_kernel's ascent step for each multiplier on its own
+// constraint (g = 2 d0 moves eta by step_eta, g = 2 d1 moves gamma by step_gamma; one momentum, one counter k).
+// state = {eta, m_eta, k, 0, gamma, m_gamma, 0, 0}; thread 0 alone reads and writes it, with ordinary stores. With gamma == 0
+// and step_gamma == 0 the loss and state[0..2] are finish_unsure_kernel's bits (a finite D1 enters as + 0).
+struct UnsurePgStep {
+    float c_mse, inv_n_div, step_eta, step_gamma, momentum;
+    int update;
+};
+__global__ __launch_bounds__(RED_THREADS) void finish_unsure_pg_kernel(const float *__restrict__ work, int nparts,
+                                                                       UnsurePgStep u, float *__restrict__ state,
+                                                                       float *__restrict__ out) {
+    __shared__ float scratch[RED_THREADS / 64];
+    float sums[3];
+    for (int q = 0; q < 3; ++q) {
+        float v = 0.f;
+        for (int i = threadIdx.x; i < nparts; i += RED_THREADS) v += work[q * SEI_REDUCE_BLOCKS + i];
+        sums[q] = sei_block_sum<RED_THREADS>(v, scratch);    // (only thread 0's value is the block sum; only it goes on)
+    }
+    if (threadIdx.x != 0) return;
+    const float eta = state[0], m_eta = state[1], k = state[2], gamma = state[4], m_gamma = state[5];
+    const float d0 = sums[0] * u.inv_n_div, d1 = sums[1] * u.inv_n_div;
+    out[0] = sums[0];
+    out[1] = sums[1];
+    out[2] = sums[2];
+    out[3] = fmaf(u.c_mse, sums[2], fmaf(2.f * gamma, d1, (2.f * eta) * d0));
+    if (u.update) {
+        const float g0 = 2.f * d0, g1 = 2.f * d1, keep = 1.f - u.momentum;
+        const float m0 = k == 0.f ? g0 : fmaf(u.momentum, m_eta, keep * g0);
+        const float m1 = k == 0.f ? g1 : fmaf(u.momentum, m_gamma, keep * g1);
+        state[0] = fmaf(u.step_eta, m0, eta);
+        state[1] = m0;
+        state[2] = k + 1.f;
+        state[4] = fmaf(u.step_gamma, m1, gamma);
+        state[5] = m1;
+    }
+}
+
 inline int reduce_blocks(size_t n) {
     size_t g = sei_ceil_div(n, (size_t)RED_THREADS * 4);
     if (g < 1) g = 1;
@@ -252,6 +360,15 @@ extern "C" int sei_axpy_sqrt_dev(const float *a, const float *b, const float *p,
     size_t grid = sei_ceil_div(n / 4 + 1, 256);
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(axpy_sqrt_dev_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, b, p, out, n);
+    return sei_launch_status();
+}
+
+extern "C" int sei_axpy_hetero_dev(const float *a, const float *b, const float *state, float *out, size_t n, void *stream) {
+    SEI_REQUIRE(a && b && state && out && n > 0);
+    SEI_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0 && ((uintptr_t)state & 3) == 0);
+    size_t grid = sei_ceil_div(n / 4 + 1, 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(axpy_hetero_dev_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, b, state, out, n);
     return sei_launch_status();
 }
 
@@ -328,6 +445,30 @@ extern "C" int sei_sure_loss_unsure(const float *y, const float *y1, const float
     u.c_mse = c_mse; u.inv_n_div = inv_n_div; u.step_size = step_size; u.momentum = momentum; u.update = update;
     hipLaunchKernelGGL(finish_unsure_kernel, dim3(1), dim3(RED_THREADS), 0, (hipStream_t)stream, (const float *)work, grid,
                        u, state, out3);
+    return sei_launch_status();
+}
+
+// sei_sure_loss_unsure with the per-pixel weight eta + gamma y (state[0], state[4]) and one ascent step per multiplier
+// (Poisson-Gaussian UNSURE). work: 3 * SEI_REDUCE_BLOCKS floats.
+extern "C" int sei_sure_loss_unsure_pg(const float *y, const float *y1, const float *y2, const float *b, int planes, int H,
+                                       int W, int margin_div, int margin_mse, float tau, float c_mse, float inv_n_div,
+                                       float step_eta, float step_gamma, float momentum, int update, float *state,
+                                       float *out4, float *g1, float *g2, float *work, void *stream) {
+    SEI_REQUIRE(y && y1 && y2 && b && out4 && g1 && g2 && work);
+    SEI_REQUIRE(planes > 0 && H > 0 && W > 0 && margin_div >= 0 && margin_mse >= 0 && tau != 0.f);
+    SEI_REQUIRE(2 * margin_div < H && 2 * margin_div < W && 2 * margin_mse < H && 2 * margin_mse < W);
+    SEI_REQUIRE(state && ((uintptr_t)state & 15) == 0);
+    SEI_REQUIRE(momentum >= 0.f && momentum < 1.f && std::isfinite(step_eta) && std::isfinite(step_gamma) &&
+                (update == 0 || update == 1));
+    const size_t total = (size_t)planes * H * W;
+    const int grid = reduce_blocks(total);
+    hipLaunchKernelGGL(sure_terms_unsure_pg_kernel, dim3(grid), dim3(RED_THREADS), 0, (hipStream_t)stream, y, y1, y2, b,
+                       total, H, W, margin_div, margin_mse, 1.0f / tau, c_mse, inv_n_div, (const float *)state, g1, g2, work);
+    UnsurePgStep u;
+    u.c_mse = c_mse; u.inv_n_div = inv_n_div; u.step_eta = step_eta; u.step_gamma = step_gamma; u.momentum = momentum;
+    u.update = update;
+    hipLaunchKernelGGL(finish_unsure_pg_kernel, dim3(1), dim3(RED_THREADS), 0, (hipStream_t)stream, (const float *)work,
+                       grid, u, state, out4);
     return sei_launch_status();
 }
 

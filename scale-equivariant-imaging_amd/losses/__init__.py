@@ -22,16 +22,24 @@ from physics._ops import axpy
 from transforms import CombinedTransform, Rotate, ScalingTransform, Shift
 from .ei import EILoss, SupLoss, mse
 from .r2r import R2REILoss
-from .sure import SureGaussianLoss, draw_probe
+from .sure import SureGaussianLoss, SurePoissonGaussianLoss, draw_probe
 
 
 UNSURE_FLAG = "--sure_unknown_noise"
+UNSURE_MODEL_FLAG = "--unsure_noise_model"
+UNSURE_NOISE_MODELS = ("gaussian", "poisson_gaussian")
 
 
 def check_unsure_args(args, world=1):
     """What --sure_unknown_noise cannot be combined with, refused by the flag's name before any GPU object exists
     (`get_loss` and train.py call this; a namespace without the attribute has the flag off)."""
+    model = getattr(args, "unsure_noise_model", "gaussian")
+    if model not in UNSURE_NOISE_MODELS:
+        raise ValueError(f"{UNSURE_MODEL_FLAG} must be one of {', '.join(UNSURE_NOISE_MODELS)}, got {model!r}")
     if not getattr(args, "sure_unknown_noise", False):
+        if model != "gaussian":
+            raise ValueError(f"{UNSURE_MODEL_FLAG} {model} names the noise model whose levels {UNSURE_FLAG} estimates: "
+                             f"pass {UNSURE_FLAG} as well")
         return
     if args.method not in ("proposed", "sure"):
         raise ValueError(f"{UNSURE_FLAG} estimates the noise level inside the SURE term: --method {args.method} has none "
@@ -45,6 +53,26 @@ def check_unsure_args(args, world=1):
     momentum = getattr(args, "unsure_momentum", 0.9)
     if not 0.0 <= momentum < 1.0:
         raise ValueError(f"--unsure_momentum must lie in [0, 1) with {UNSURE_FLAG}, got {momentum}")
+    if model == "poisson_gaussian" and args.method == "proposed" and not getattr(args, "ProposedLoss__stop_gradient", True):
+        raise ValueError(f"--no-ProposedLoss__stop_gradient cannot be combined with {UNSURE_MODEL_FLAG} poisson_gaussian: the "
+                         "equivariant branch's noise level then depends on A(T x_net), and no kernel differentiates it")
+
+
+def _sure_term(noise_level, cropped_div, averaged_cst, margin, unsure, unsure_step_size, unsure_momentum, unsure_noise_model,
+               unsure_init_gain, unsure_gain_step_size):
+    """The SURE term of SURELoss and ProposedLoss: SureGaussianLoss as before, or (unsure with the Poisson-Gaussian model)
+    SurePoissonGaussianLoss."""
+    if unsure_noise_model not in UNSURE_NOISE_MODELS:
+        raise ValueError(f"unsure_noise_model ({UNSURE_MODEL_FLAG}) must be one of {UNSURE_NOISE_MODELS}, "
+                         f"got {unsure_noise_model!r}")
+    if unsure_noise_model == "poisson_gaussian":
+        if not unsure:
+            raise ValueError(f"unsure_noise_model='poisson_gaussian' ({UNSURE_MODEL_FLAG}) needs unsure ({UNSURE_FLAG})")
+        return SurePoissonGaussianLoss(sigma=noise_level / 255, gain=unsure_init_gain, cropped_div=cropped_div,
+                                       averaged_cst=averaged_cst, margin=margin, step_size=unsure_step_size,
+                                       gain_step_size=unsure_gain_step_size, momentum=unsure_momentum)
+    return SureGaussianLoss(sigma=noise_level / 255, cropped_div=cropped_div, averaged_cst=averaged_cst, margin=margin,
+                            unsure=unsure, step_size=unsure_step_size, momentum=unsure_momentum)
 
 
 def _stochastic_depth_masks(model, batch):
@@ -124,10 +152,9 @@ class Noise2InverseLoss(_ModelPlusOneLoss):
 
 class SURELoss(_ModelPlusOneLoss):
     def __init__(self, noise_level, cropped_div, averaged_cst, margin, physics, unsure=False, unsure_step_size=1e-4,
-                 unsure_momentum=0.9):
-        super().__init__(physics, SureGaussianLoss(sigma=noise_level / 255, cropped_div=cropped_div,
-                                                   averaged_cst=averaged_cst, margin=margin, unsure=unsure,
-                                                   step_size=unsure_step_size, momentum=unsure_momentum))
+                 unsure_momentum=0.9, unsure_noise_model="gaussian", unsure_init_gain=0.0, unsure_gain_step_size=None):
+        super().__init__(physics, _sure_term(noise_level, cropped_div, averaged_cst, margin, unsure, unsure_step_size,
+                                             unsure_momentum, unsure_noise_model, unsure_init_gain, unsure_gain_step_size))
 
     def draw(self, y, model=None):
         first = _stochastic_depth_masks(model, y.shape[0])                       # model(y)
@@ -184,14 +211,20 @@ class ProposedLoss(Module):
 
     def __init__(self, blueprint, sure_alternative, noise_level, stop_gradient, sure_cropped_div,
                  sure_averaged_cst, sure_margin, alpha_tradeoff, transforms, physics, fuse_passes=None, unsure=False,
-                 unsure_step_size=1e-4, unsure_momentum=0.9):
+                 unsure_step_size=1e-4, unsure_momentum=0.9, unsure_noise_model="gaussian", unsure_init_gain=0.0,
+                 unsure_gain_step_size=None):
         """unsure: the SURE term estimates the noise level (SureGaussianLoss(unsure=True)); it runs before the EI term in
-        both pass orders, and the EI branch's measurement noise takes the level as the SURE term left it this step."""
+        both pass orders, and the EI branch's measurement noise takes the level as the SURE term left it this step.
+        unsure_noise_model "poisson_gaussian": the term is SurePoissonGaussianLoss (two levels, started from `noise_level`
+        and `unsure_init_gain`), and the EI branch's noise is signal-dependent; it needs stop_gradient."""
         super().__init__()
         self.physics = physics
         self.graph_safe = False
         if unsure and sure_alternative == "r2r":
             raise ValueError(f"unsure ({UNSURE_FLAG}) has no SURE term to work in under sure_alternative='r2r'")
+        if unsure_noise_model == "poisson_gaussian" and not stop_gradient:
+            raise ValueError(f"unsure_noise_model='poisson_gaussian' ({UNSURE_MODEL_FLAG}) needs stop_gradient: "
+                             "--no-ProposedLoss__stop_gradient would differentiate the signal-dependent noise level")
         if transforms == "Scaling_Transforms":
             ei_transform = ScalingTransform(**blueprint[ScalingTransform.__name__])
         elif transforms == "Shifts":
@@ -209,9 +242,8 @@ class ProposedLoss(Module):
             self.compute_x_net = False
             self.fuse_passes = False
             return
-        self.sure = SureGaussianLoss(sigma=noise_level / 255, cropped_div=sure_cropped_div,
-                                     averaged_cst=sure_averaged_cst, margin=sure_margin, unsure=unsure,
-                                     step_size=unsure_step_size, momentum=unsure_momentum)
+        self.sure = _sure_term(noise_level, sure_cropped_div, sure_averaged_cst, sure_margin, unsure, unsure_step_size,
+                               unsure_momentum, unsure_noise_model, unsure_init_gain, unsure_gain_step_size)
         self.ei = EILoss(metric=mse(), transform=ei_transform, no_grad=stop_gradient, weight=alpha_tradeoff)
         self.loss_fns = [self.sure, self.ei]
         self.compute_x_net = True
@@ -304,7 +336,8 @@ class ProposedLoss(Module):
         if self.compute_x_net and self.sure.unsure:
             # the estimated level, read from device memory when the EI term's noise kernel runs: after the SURE term's
             # update of this step in both pass orders below (self.loss_fns lists the SURE term first)
-            ei_kw["noise_sigma2"] = self.sure.noise_state
+            pg = isinstance(self.sure, SurePoissonGaussianLoss)
+            ei_kw["noise_state_pg" if pg else "noise_sigma2"] = self.sure.noise_state
         drop = draws.get("drop") if draws is not None else None
         calls = [model] * 3 if drop is None else [_with_masks(model, m) for m in drop]
         if not self.fuse_passes:
@@ -341,11 +374,14 @@ class ProposedLoss(Module):
 
 class Loss(Module):
     def __init__(self, physics, blueprint, noise_level, sure_cropped_div, sure_averaged_cst, sure_margin,
-                 method, crop_training_pairs, crop_size, unsure=False, unsure_step_size=1e-4, unsure_momentum=0.9):
+                 method, crop_training_pairs, crop_size, unsure=False, unsure_step_size=1e-4, unsure_momentum=0.9,
+                 unsure_noise_model="gaussian", unsure_init_gain=0.0, unsure_gain_step_size=None):
         super().__init__()
         if unsure and method not in ("proposed", "sure"):
             raise ValueError(f"unsure ({UNSURE_FLAG}) needs a SURE term: method {method!r} has none")
-        unsure_kw = dict(unsure=unsure, unsure_step_size=unsure_step_size, unsure_momentum=unsure_momentum)
+        unsure_kw = dict(unsure=unsure, unsure_step_size=unsure_step_size, unsure_momentum=unsure_momentum,
+                         unsure_noise_model=unsure_noise_model, unsure_init_gain=unsure_init_gain,
+                         unsure_gain_step_size=unsure_gain_step_size)
         if method == "supervised":
             self.loss = SupervisedLoss(physics=physics)
         elif method == "css":
@@ -371,7 +407,8 @@ class Loss(Module):
             self.crop_fn = None
 
     def unsure_term(self):
-        """The SURE term that estimates the noise level (it owns `noise_state` and `estimated_sigma`), or None."""
+        """The SURE term that estimates the noise level (it owns `noise_state` and `estimated_sigma`; with the
+        Poisson-Gaussian model also `estimated_gain`), or None."""
         term = getattr(self.loss, "sure", None) or getattr(self.loss, "loss", None)
         return term if isinstance(term, SureGaussianLoss) and term.unsure else None
 
@@ -428,4 +465,7 @@ def get_loss(args, physics):
     return Loss(physics=physics, blueprint=blueprint, method=args.method, noise_level=noise_level,
                 sure_cropped_div=args.sure_cropped_div, sure_averaged_cst=args.sure_averaged_cst,
                 sure_margin=sure_margin, unsure=unsure, unsure_step_size=getattr(args, "unsure_step_size", 1e-4),
-                unsure_momentum=getattr(args, "unsure_momentum", 0.9), **blueprint[Loss.__name__])
+                unsure_momentum=getattr(args, "unsure_momentum", 0.9),
+                unsure_noise_model=getattr(args, "unsure_noise_model", "gaussian"),
+                unsure_init_gain=getattr(args, "unsure_init_gain", 0.0),
+                unsure_gain_step_size=getattr(args, "unsure_gain_step_size", None), **blueprint[Loss.__name__])

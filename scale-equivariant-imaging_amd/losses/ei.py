@@ -61,11 +61,14 @@ class EILoss(Module):
         self.noise = apply_noise
         self.no_grad = no_grad
 
-    def forward(self, x_net, physics, model, transform_params=None, noise=None, noise_sigma2=None, **kwargs):
+    def forward(self, x_net, physics, model, transform_params=None, noise=None, noise_sigma2=None, noise_state_pg=None,
+                **kwargs):
         """transform_params / noise: the transform's draws and the unit measurement noise, when the caller has
         drawn them already (losses.ProposedLoss.draw); drawn here otherwise, as deepinv does.
         noise_sigma2: a float32 device tensor whose first element stands for sigma^2 of the measurement noise in the
-        place of the physics' own level (UNSURE: losses/sure.py's `noise_state`, read by the kernel at run time)."""
+        place of the physics' own level (UNSURE: losses/sure.py's `noise_state`, read by the kernel at run time).
+        noise_state_pg: the eight-float state of SurePoissonGaussianLoss instead: the variance of the measurement noise at a
+        pixel is state[0] + state[4] A(x2) (needs no_grad: the level then depends on x2, and that is not differentiated)."""
         T = self.T if transform_params is None else (lambda v: self.T(v, params=transform_params))
         if self.no_grad:
             with torch.no_grad():
@@ -74,6 +77,8 @@ class EILoss(Module):
             x2 = T(x_net)
         if not self.noise:
             y2 = physics.A(x2)
+        elif noise_state_pg is not None:
+            y2 = physics.noise_model(physics.A(x2), noise=noise, noise_state_pg=noise_state_pg)
         elif noise_sigma2 is not None:
             y2 = physics.noise_model(physics.A(x2), noise=noise, noise_sigma2=noise_sigma2)
         elif noise is None:

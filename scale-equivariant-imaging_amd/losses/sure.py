@@ -9,6 +9,8 @@ sigma^2 / batch_size. The two interior reductions and both gradients come out of
 
 `SureGaussianLoss(unsure=True)` is the same term for an UNKNOWN noise level (UNSURE; restated from the paper, see the
 constructor): sigma^2 becomes a multiplier in device memory that `sei_sure_loss_unsure` reads and moves by gradient ascent.
+`SurePoissonGaussianLoss` is that term for Poisson-Gaussian noise, variance sigma^2 + gain * signal with both levels unknown:
+two multipliers, the weight eta + gamma y inside the divergence (`sei_sure_loss_unsure_pg`).
 """
 import torch
 import torch.nn as nn
@@ -17,9 +19,9 @@ import _native as N
 from physics._ops import axpy
 
 
-def _terms_buffers(ctx, y, y1, y2, b, margin_div, margin_mse):
-    """What both SURE entry points take: the operands checked, the outputs and the gradients allocated and saved on `ctx`.
-    -> (n_div, n_mse, out3, work, (y1, y2, g1, g2 pointers))."""
+def _terms_buffers(ctx, y, y1, y2, b, margin_div, margin_mse, nsums=2):
+    """What the SURE entry points take: the operands checked, the outputs and the gradients allocated and saved on `ctx`.
+    -> (n_div, n_mse, out, work, (y1, y2, g1, g2 pointers)); `out` holds the `nsums` sums and the loss value behind them."""
     joint = y2 is None
     B, C, H, W = y.shape
     for name, t in (("y", y), ("y1", y1), ("b", b)) + (() if joint else (("y2", y2),)):
@@ -28,8 +30,8 @@ def _terms_buffers(ctx, y, y1, y2, b, margin_div, margin_mse):
             raise ValueError("SURE: y, A(x_net), A(f(y + tau b)) and b must share one shape")
     n_div = B * C * (H - 2 * margin_div) * (W - 2 * margin_div)
     n_mse = B * C * (H - 2 * margin_mse) * (W - 2 * margin_mse)
-    out = torch.empty(3, dtype=torch.float32, device=y.device)
-    work = torch.empty(2 * N.SEI_REDUCE_BLOCKS, dtype=torch.float32, device=y.device)
+    out = torch.empty(nsums + 1, dtype=torch.float32, device=y.device)
+    work = torch.empty(nsums * N.SEI_REDUCE_BLOCKS, dtype=torch.float32, device=y.device)
     if joint:
         g = torch.empty_like(y1)
         half = y.numel() * y.element_size()
@@ -91,6 +93,29 @@ class _UnsureTerms(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go):
         return _scaled_terms_grads(ctx, go, 11)
+
+
+class _UnsurePgTerms(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, y1, y2, b, margin_div, margin_mse, tau, state, step_eta, step_gamma, momentum, update):
+        """_UnsureTerms with the per-pixel weight eta + gamma y, eta = state[0] and gamma = state[4] in device memory
+        (sei_sure_loss_unsure_pg): loss = c_mse * mse_sum + 2 (eta * div_sum + gamma * ydiv_sum) / n_div, the gradients carry
+        both multipliers as they stand on entry, and with `update` the kernel's last stage then moves `state` =
+        {eta, m_eta, k, 0, gamma, m_gamma, 0, 0} one ascent step each, in place. No gradient reaches `state`."""
+        B, C, H, W = y.shape
+        N.check_tensor(state, "noise_state")
+        if state.numel() != 8 or state.device != y.device:
+            raise ValueError("UNSURE: the Poisson-Gaussian noise_state must hold eight floats on the device of y (move the "
+                             "loss module there)")
+        n_div, n_mse, out, work, ptrs = _terms_buffers(ctx, y, y1, y2, b, margin_div, margin_mse, nsums=3)
+        N.call("sei_sure_loss_unsure_pg", y.data_ptr(), ptrs[0], ptrs[1], b.data_ptr(), B * C, H, W, margin_div, margin_mse,
+               tau, 1.0 / n_mse, 1.0 / n_div, float(step_eta), float(step_gamma), float(momentum), int(bool(update)),
+               state.data_ptr(), out.data_ptr(), ptrs[2], ptrs[3], work.data_ptr())
+        return out[3]
+
+    @staticmethod
+    def backward(ctx, go):
+        return _scaled_terms_grads(ctx, go, 12)
 
 
 def draw_probe(y, margin):
@@ -176,3 +201,33 @@ class SureGaussianLoss(nn.Module):
             assert physics.rate is not None
             return physics.rate**2 * loss
         return loss
+
+
+class SurePoissonGaussianLoss(SureGaussianLoss):
+    def __init__(self, sigma, gain=0.0, tau=1e-2, margin=0, cropped_div=False, averaged_cst=False, step_size=1e-4,
+                 gain_step_size=None, momentum=0.9):
+        """UNSURE for Poisson-Gaussian noise, variance sigma^2 + gain * (clean value) at a pixel, with BOTH levels unknown
+        (the same paper's signal-dependent case; restated from it -- parity with deepinv's SurePGLoss(unsure=True) is
+        unpinned). The multiplier becomes the affine weight eta + gamma y inside the divergence, one multiplier per
+        zero-expected-divergence constraint, each with SureGaussianLoss(unsure=True)'s ascent step:
+
+            loss = mean_int((A(x_net) - y)^2) + 2 (eta d0 + gamma d1)
+            d0 = mean_int(b * (A(f(y + tau b)) - A(x_net)) / tau),   d1 = mean_int(y * b * (A(f(y + tau b)) - A(x_net)) / tau)
+            per multiplier: g = 2 d;  m' = g on the first step, else momentum * m + (1 - momentum) * g;  value' = value + step * m'
+
+        (no second-order term, no third model call). eta starts at `sigma`^2 and moves by `step_size`, gamma at `gain` by
+        `gain_step_size` (default: `step_size`). The state {eta, m_eta, k, 0, gamma, m_gamma, 0, 0} is the float32 buffer
+        `noise_state`, as the parent's: slots 0..2 keep their meaning."""
+        super().__init__(sigma, tau=tau, margin=margin, cropped_div=cropped_div, averaged_cst=averaged_cst, unsure=True,
+                         step_size=step_size, momentum=momentum)
+        self.name = "SurePoissonGaussian"
+        self.gain_step_size = self.step_size if gain_step_size is None else float(gain_step_size)
+        self.noise_state = torch.tensor([self.sigma2, 0.0, 0.0, 0.0, float(gain), 0.0, 0.0, 0.0], dtype=torch.float32)
+
+    def estimated_gain(self):
+        """gamma as a host float, as it stands (not clamped): a synchronisation, for use outside the step only."""
+        return float(self.noise_state[4])
+
+    def _terms(self, y, y1, y2, b):
+        return _UnsurePgTerms.apply(y, y1, y2, b, self.div_margin, self.margin, self.tau, self.noise_state, self.step_size,
+                                    self.gain_step_size, self.momentum, self.training)

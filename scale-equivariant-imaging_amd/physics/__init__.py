@@ -10,7 +10,7 @@ from os.path import exists
 import torch
 
 from rng import fork_rng
-from ._base import GaussianNoise, LinearPhysics
+from ._base import GaussianNoise, LinearPhysics, PoissonGaussianNoise
 from .blur import Blur, BlurV2
 from .ct_like_filter import CTLikeFilter
 from .downsampling import Downsampling
@@ -32,7 +32,7 @@ class BlurKernel:
 
 
 class PhysicsManager:
-    def __init__(self, blueprint, task, device, noise_level, v2, blur_padding="circular"):
+    def __init__(self, blueprint, task, device, noise_level, v2, blur_padding="circular", noise_gain=0.0):
         if task == "deblurring":
             kernel = BlurKernel(**blueprint[BlurKernel.__name__]).to_tensor(device)
             # (the FFT operator BlurV2 stands for has no boundary but the circular one)
@@ -47,7 +47,10 @@ class PhysicsManager:
         else:
             raise ValueError(f"Unknown task: {task}")
 
-        physics.noise_model = GaussianNoise(sigma=noise_level / 255)
+        if noise_gain > 0:      # --noise_gain: Poisson-Gaussian measurements, variance (noise_level / 255)^2 + gain * A(x)
+            physics.noise_model = PoissonGaussianNoise(sigma=noise_level / 255, gain=noise_gain)
+        else:
+            physics.noise_model = GaussianNoise(sigma=noise_level / 255)
         self.task = task
         physics.task = task
         setattr(physics, "__manager", self)
@@ -67,7 +70,8 @@ class PhysicsManager:
 def get_physics(args, device):
     blueprint = {
         PhysicsManager.__name__: {"task": args.task, "noise_level": args.noise_level, "v2": args.physics_v2,
-                                   "blur_padding": getattr(args, "blur_padding", "circular")},
+                                   "blur_padding": getattr(args, "blur_padding", "circular"),
+                                   "noise_gain": float(getattr(args, "noise_gain", 0.0) or 0.0)},
         BlurKernel.__name__: {"kernel_path": args.kernel},
         Downsampling.__name__: {"rate": args.sr_factor, "true_adjoint": args.physics_true_adjoint},
     }

@@ -308,3 +308,36 @@ def axpy_sqrt_dev(a, b, sigma2):
     """a + sqrt(max(sigma2[0], 0)) * b with `sigma2` read from device memory by the kernel (measurement noise at a level
     that a captured step moves: losses/sure.py's `noise_state`). No gradient reaches `sigma2`."""
     return _AxpySqrtDev.apply(a, b, sigma2)
+
+
+class _AxpyHeteroDev(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, state):
+        N.check_tensor(a, "a")
+        N.check_tensor(b, "b")
+        N.check_tensor(state, "state")
+        if a.shape != b.shape:
+            raise ValueError("axpy: shape mismatch")
+        if state.numel() != 8 or state.device != a.device:
+            raise ValueError("axpy: state must hold the eight floats of the Poisson-Gaussian noise state on the device of "
+                             "the operands")
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            # d out / d a = 1 + gamma b / (2 sqrt(eta + gamma a)) where the root's argument is positive: no kernel computes
+            # it, and nothing here stands in for one (train.py refuses --no-ProposedLoss__stop_gradient with this model)
+            raise NotImplementedError("axpy_hetero_dev: the signal-dependent noise level is not differentiated; call it on "
+                                      "operands that need no gradient (EILoss(no_grad=True))")
+        a, b = (t if N.aligned(t) else t.clone() for t in (a, b))       # (as _Axpy: float4 reads and writes)
+        out = torch.empty_like(a)
+        N.call("sei_axpy_hetero_dev", a.data_ptr(), b.data_ptr(), state.data_ptr(), out.data_ptr(), a.numel())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, None, None
+
+
+def axpy_hetero_dev(a, b, state):
+    """a_i + sqrt(max(state[0] + state[4] a_i, 0)) * b_i with `state` read from device memory by the kernel: measurement
+    noise whose variance is affine in the signal (Poisson-Gaussian), at the two levels that a captured step moves
+    (losses/sure.py's SurePoissonGaussianLoss.noise_state). Operands that need no gradient only."""
+    return _AxpyHeteroDev.apply(a, b, state)

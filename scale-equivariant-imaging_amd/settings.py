@@ -15,6 +15,9 @@ class DefaultArgParser(ArgumentParser):
         flag("--physics_true_adjoint", default=False, **onoff)
         flag("--sr_factor", type=int, default=None)
         flag("--noise_level", type=int, default=5)
+        # build-side addition: Poisson-Gaussian measurements, variance (noise_level / 255)^2 + G * A(x) with images in
+        # [0, 1] (physics._base.PoissonGaussianNoise); 0 keeps the Gaussian model
+        flag("--noise_gain", type=float, default=0.0)
         flag("--dataset", type=str, default="div2k")
         flag("--GroundTruthDataset__datasets_dir", type=str, default="./datasets")
         flag("--GroundTruthDataset__download", "--download", default=False, **onoff)

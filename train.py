@@ -32,6 +32,10 @@ step runs in libsei_hip.so. Differences, all build-side and documented in DESIGN
     `--unsure_init_noise_level` (default `--noise_level`) and moved by the loss kernel itself every step
     (`--unsure_step_size`, `--unsure_momentum`), so the step still replays from a hipGraph; the csv gets a third column
     `Estimated Noise Level` and the checkpoints a key `loss_state`, which `--RESUME` restores. One GPU.
+    `--unsure_noise_model poisson_gaussian` estimates the two levels of Poisson-Gaussian noise (variance sigma^2 + gain *
+    signal) instead: a second multiplier started from `--unsure_init_gain` and moved by `--unsure_gain_step_size`, a fourth
+    csv column `Estimated Noise Gain`, eight floats in `loss_state`. `--noise_gain G` (settings.py) makes the synthetic
+    measurements Poisson-Gaussian.
 """
 import csv
 import os
@@ -121,6 +125,13 @@ def build_parser():
     flag("--unsure_init_noise_level", type=float, default=None,
          help="starting guess of the noise level on --noise_level's 0..255 scale (default: --noise_level, which keeps "
               "generating the synthetic measurements)")
+    flag("--unsure_noise_model", choices=["gaussian", "poisson_gaussian"], default="gaussian",
+         help="what --sure_unknown_noise estimates: one constant level, or (poisson_gaussian) the two levels of a variance "
+              "sigma^2 + gain * signal, with a fourth csv column for the gain")
+    flag("--unsure_init_gain", type=float, default=0.0,
+         help="starting guess of the gain, in image units with images in [0, 1] (--unsure_noise_model poisson_gaussian)")
+    flag("--unsure_gain_step_size", type=float, default=None,
+         help="ascent step of the gain's multiplier (default: --unsure_step_size)")
     flag("--device_cache", default=False, **onoff,
          help="keep every (x, y) training pair in HBM (deterministic measurements) and draw crops on the device "
               "instead of the per-item DataLoader path (datasets/device_cache.py)")
@@ -203,6 +214,7 @@ def main(argv=None):
 
     loss = get_loss(args=args, physics=physics)
     unsure = loss.unsure_term()                       # the SURE term that owns the estimated noise level, or None
+    unsure_pg = unsure is not None and args.unsure_noise_model == "poisson_gaussian"       # ... and the estimated gain
     if unsure is not None:
         unsure.to(args.device)
     if isdir(args.dataset):
@@ -284,7 +296,8 @@ def main(argv=None):
         os.makedirs(args.out_dir, exist_ok=True)
         file = open(f"{args.out_dir}/training.csv", "w", newline="", buffering=1)
         log = csv.writer(file)
-        log.writerow(["Epoch", "Training Loss"] + (["Estimated Noise Level"] if unsure is not None else []))
+        log.writerow(["Epoch", "Training Loss"] + (["Estimated Noise Level"] if unsure is not None else [])
+                     + (["Estimated Noise Gain"] if unsure_pg else []))
 
     scheduler_disabled = False
     if args.RESUME is not None:
@@ -302,10 +315,18 @@ def main(argv=None):
         if unsure is not None:
             if "loss_state" not in ckp:
                 raise ValueError(f"--sure_unknown_noise: {args.RESUME} holds no loss_state (it was written without the flag)")
+            stored, own = ckp["loss_state"].get("noise_state"), unsure.noise_state
+            if stored is not None and stored.numel() != own.numel():
+                raise ValueError(f"--unsure_noise_model {args.unsure_noise_model}: the loss_state of {args.RESUME} holds "
+                                 f"{stored.numel()} floats, this noise model's holds {own.numel()} (4: gaussian, 8: "
+                                 "poisson_gaussian); resume with the model the checkpoint was written with")
             unsure.load_state_dict(ckp["loss_state"])         # in place: a captured step reads the buffer's address
     if unsure is not None and os.environ.get("SEI_TRACE_UNSURE_STATE") == "1" and rank == 0:
         eta, m, k = unsure.noise_state[:3].tolist()           # tests: what the first step starts from
         print(f"unsure state at start: eta {eta!r} m {m!r} k {k!r}")
+        if unsure_pg:
+            gamma, m_gamma = unsure.noise_state[4:6].tolist()
+            print(f"unsure gain state at start: gamma {gamma!r} m_gamma {m_gamma!r}")
 
     def loss_state():
         return None if unsure is None else unsure.state_dict()
@@ -403,6 +424,10 @@ def main(argv=None):
                 estimate = 255 * unsure.estimated_sigma()     # (a sync, once per epoch and outside the step)
                 line += f"\tEstimated_Noise_Level: {estimate:.3f}"
                 row.append(estimate)
+            if unsure_pg:
+                gain = unsure.estimated_gain()
+                line += f"\tEstimated_Noise_Gain: {gain:.3e}"
+                row.append(gain)
             print(line)
             log.writerow(row)
             if (epoch % checkpoint_interval == 0) or (epoch == epochs - 1):
