@@ -307,6 +307,38 @@ int sei_luma_sqerr(const float *a, const float *b, size_t npix, float *out1, flo
 int sei_ssim_luma(const float *a, const float *b, int batch, int H, int W, float *out, float *work, void *stream);
 size_t sei_ssim_luma_work_floats(int batch, int H, int W);
 
+/* Equivariant bootstrap of the evaluation step (csrc/bootstrap_kernels.hip, bootstrap.py; Tachella and Pereyra,
+ * "Equivariant bootstrapping for uncertainty quantification in imaging inverse problems", restated from the paper: no
+ * package is ported and no parity with one is claimed). For replica r the host forms a_r = T_r x, measures it again through
+ * the physics with fresh noise, reconstructs it as b_r, and takes the error of b_r against a_r as a sample of the error of x
+ * against the truth. T_r is the padded zoom-out of the EI loss (bicubic A = -0.75, reflection, align_corners=True) by
+ * rate[r] about (center[2r], center[2r + 1]) = (cx, cy). All three work on a grid laid out by rows and columns: pixel
+ * (i, j) has the base coordinates x = (2 / W) j - 1, y = (2 / H) i - 1, in scale_taps' float32 operation order
+ * (sei_scale_resample_fwd keeps the reference's transposed meshgrid; where H == W the two are the same bits).
+ *   sei_boot_scale_fwd: y[r] = T_r x for r < B, sampled at (g - c) / rate + c. x is ONE (C, H, W) image that every replica
+ *     reads; y is (B, C, H, W). The taps of a pixel are computed once for all channels.
+ *   sei_boot_luma_diff: d[i] = Y(q(a_i)) - Y(q(b_i)) per pixel and out[i] = the sum of d[i]^2 over the image, for `batch`
+ *     planar images a, b of shape (3, npix), contiguous, 4-byte aligned. q(t) = min(max(rintf(t * 255) / 255, 0), 1) with a
+ *     correctly rounded division and ties to even (test.py's quantize_and_clamp in float32, bit for bit),
+ *     Y = 0.299 R + 0.587 G + 0.114 B unfused and left to right (sei_luma_sqerr's). d is (batch, npix). `work` holds
+ *     sei_boot_luma_diff_work_floats(batch, npix) floats (0 = arguments refused): the per-workgroup sums, which one wave per
+ *     image adds in index order, in double. No atomics; an image's workgroups depend on npix alone, so its sum does not
+ *     depend on the batch it is in.
+ *   sei_boot_pullback_accum: msq[p] = (accumulate ? msq[p] : 0) + sum_{r < B} v_r^2, v_r the same bicubic gather from the
+ *     (H, W) plane d[r] at rate (g - c) + c (the sample points lie inside the image; taps past the border reflect), added
+ *     in the order of r as acc = fmaf(v_r, v_r, acc): calls over consecutive chunks of replicas, the later ones with
+ *     accumulate != 0, leave the bits of one call over all of them. The gather is an interpolating pull-back, not the
+ *     inverse of T_r. One thread per pixel.
+ * SEI_ERR_BAD_ARG on NULL pointers, non-positive counts, 2^30 pixels or more per plane (npix of sei_boot_luma_diff
+ * included), more than 65535 images in sei_boot_luma_diff; nothing is launched then. */
+int sei_boot_scale_fwd(const float *x, float *y, const float *rate, const float *center, int B, int C, int H, int W,
+                       void *stream);
+int sei_boot_luma_diff(const float *a, const float *b, int batch, size_t npix, float *d, float *out, float *work,
+                       void *stream);
+size_t sei_boot_luma_diff_work_floats(int batch, size_t npix);
+int sei_boot_pullback_accum(const float *d, const float *rate, const float *center, int B, int H, int W, float *msq,
+                            int accumulate, void *stream);
+
 /* LPIPS v0.1 on AlexNet features (csrc/lpips_kernels.hip; reference src/metrics.py: pyiqa.create_metric("lpips")), float32.
  * For an H x W RGB image in [0, 1] (H, W >= 31: below that the second pool has nothing to work on):
  *   v = ((2 x - 1) - shift) / scale per channel, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450);

@@ -57,6 +57,9 @@ SIGNATURES = {
     "sei_axpy_hetero_dev": [_P, _P, _P, _P, _Z, _P],
     "sei_luma_sqerr": [_P, _P, _Z, _P, _P, _P],
     "sei_ssim_luma": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "sei_boot_scale_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "sei_boot_luma_diff": [_P, _P, _I, _Z, _P, _P, _P, _P],
+    "sei_boot_pullback_accum": [_P, _P, _P, _I, _I, _I, _P, _I, _P],
     "sei_lpips_conv_relu": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "sei_lpips_maxpool": [_P, _P, _I, _I, _I, _I, _P],
     "sei_lpips_layer_dist": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P],
@@ -227,6 +230,7 @@ SIZE_QUERIES = {
     "sei_resample_sepband_lds": [_I, _I, _I, _I, _I, _I, _I, _I],
     "sei_proposed_draws_max_numel": [],
     "sei_ssim_luma_work_floats": [_I, _I, _I],
+    "sei_boot_luma_diff_work_floats": [_I, _Z],
     "sei_lpips_work_floats": [_I, _I, _I],
     "sei_tv_prox_work_floats": [_I, _I, _I],
     "sei_dip_work_floats": [_I, _I, _I, _I],

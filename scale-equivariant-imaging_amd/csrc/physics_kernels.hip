@@ -16,6 +16,7 @@
 // One launch, one workgroup per (plane, strip of 32 output columns): the row pass result lives in LDS until the column
 // pass has consumed it (see circ_filter_sep_kernel).
 #include "sei_common.h"
+#include "bicubic_taps.h"
 
 #include <atomic>
 
@@ -280,30 +281,6 @@ __global__ __launch_bounds__(RS_THREADS) void resample_sepband_kernel(
 // (__f*_rn intrinsics) so that the sampling positions agree with torch to the last bit wherever
 // the division and reciprocal are correctly rounded.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float cubic1(float x) {   // |x| <= 1, A = -0.75
-    const float A = -0.75f;
-    return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
-}
-__device__ __forceinline__ float cubic2(float x) {   // 1 < |x| < 2
-    const float A = -0.75f;
-    return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
-}
-__device__ __forceinline__ int reflect_clip(int v, int n) {
-    // reflect_coordinates(v, 0, 2(n-1)) then clip, on an integer tap position
-    if (n == 1) return 0;
-    const int span = n - 1;
-    v = v < 0 ? -v : v;
-    const int flips = v / span;
-    const int extra = v - flips * span;
-    const int r = (flips & 1) ? span - extra : extra;
-    return min(max(r, 0), n - 1);
-}
-
-struct ScaleTaps {
-    int xs[4], ys[4];
-    float wx[4], wy[4];
-};
-
 // (H, W): output / grid size; (Hi, Wi): size of the sampled image (they differ only for the
 // antialiased variant, where the reference samples the pre-shrunk image on the original-size grid)
 __device__ __forceinline__ void scale_taps(int p, int H, int W, int Hi, int Wi, float two_over_h,
@@ -315,19 +292,7 @@ __device__ __forceinline__ void scale_taps(int p, int H, int W, int Hi, int Wi, 
     const float u = __fsub_rn(__fmul_rn(two_over_w, (float)aa), 1.f);
     const float gx = __fadd_rn(__fmul_rn(inv_rate, __fsub_rn(v, cx)), cx);
     const float gy = __fadd_rn(__fmul_rn(inv_rate, __fsub_rn(u, cy)), cy);
-    const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(gx, 1.f), 2.f), (float)(Wi - 1));
-    const float iy = __fmul_rn(__fdiv_rn(__fadd_rn(gy, 1.f), 2.f), (float)(Hi - 1));
-    const float fx = floorf(ix), fy = floorf(iy);
-    const float tx = ix - fx, ty = iy - fy;
-    tp.wx[0] = cubic2(tx + 1.f); tp.wx[1] = cubic1(tx); tp.wx[2] = cubic1(1.f - tx); tp.wx[3] = cubic2(2.f - tx);
-    tp.wy[0] = cubic2(ty + 1.f); tp.wy[1] = cubic1(ty); tp.wy[2] = cubic1(1.f - ty); tp.wy[3] = cubic2(2.f - ty);
-    // clamp before the int conversion: far-out-of-range coordinates only arise from absurd rates
-    const int bx = (int)fminf(fmaxf(fx, -1.0e8f), 1.0e8f), by = (int)fminf(fmaxf(fy, -1.0e8f), 1.0e8f);
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        tp.xs[d] = reflect_clip(bx - 1 + d, Wi);
-        tp.ys[d] = reflect_clip(by - 1 + d, Hi);
-    }
+    bicubic_taps(gx, gy, Hi, Wi, tp);       // bicubic_taps.h
 }
 
 __global__ __launch_bounds__(256) void scale_resample_fwd_kernel(

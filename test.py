@@ -34,6 +34,18 @@ physics with a blur kernel, so --task sr and a folder of measurements are refuse
 DiffPIR loop on the reflect-padded measurement, cropped afterwards as the reference's wrapper does, with the diffusion U-Net
 of deepinv's DiffUNet(large_model=False) on the sei_adm_* kernels as its denoiser; FILE is the state dict of the FFHQ
 checkpoint deepinv fetches, supplied by the user and never fetched here; without the flag the kind raises and names it).
+`--bootstrap N [--bootstrap_batch B] [--bootstrap_maps]` (build-side addition; bootstrap.py: the equivariant bootstrap of
+Tachella and Pereyra, restated from the paper) estimates every image's error from its measurement alone, with or without
+ground truth: N times the estimate is zoomed out by a random rate about a random centre (the EI loss's draws), measured again
+through the physics with fresh noise and reconstructed again, B replicas per model call (default 8; a model kind that takes
+one image at a time needs 1), on the sei_boot_* kernels; the replicas go through the plain model call, also under
+--noise2inverse and --r2r. The bootstrap of image i draws under a forked generator seeded with i, so every other line of
+the output is what it is without the flag. `BOOTSTRAP_i: EST_PSNR, EST_PSNR_Q90` per image under
+--print_all_metrics, and `EST_N`, `EST_PSNR`, `EST_PSNR std`, `EST_PSNR_Q90` at the end; with a folder of measurements the
+physics of --task / --kernel / --sr_factor / --noise_level is built for the bootstrap alone. --bootstrap_maps (needs --out_dir)
+writes error_maps/NAME.npy (float32 root-mean-square error per pixel) and NAME.png (the same over its own maximum): a
+qualitative picture of where the errors sit. Calibration of EST_PSNR against the true PSNR is not shown in this build (no
+trained weights); on a dataset with ground truth both are printed side by side.
 """
 import os
 import sys
@@ -50,6 +62,7 @@ from datasets._io import read_image  # noqa: E402
 from metrics import LPIPS, compute_metrics  # noqa: E402
 from models import get_model  # noqa: E402
 from physics import get_physics  # noqa: E402
+from rng import fork_rng  # noqa: E402
 from settings import DefaultArgParser  # noqa: E402
 from training import get_weights  # noqa: E402
 
@@ -80,6 +93,9 @@ def build_parser():
     flag("--diffunet_weights", type=str, default=None, metavar="FILE")                   # build-side addition
     flag("--diffpir_iterations", type=int, default=100)                                  # build-side addition
     flag("--dps_iterations", type=int, default=1000)                                     # build-side addition
+    flag("--bootstrap", type=int, default=0, metavar="N")                                # build-side addition
+    flag("--bootstrap_batch", type=int, default=8, metavar="B")                          # build-side addition
+    flag("--bootstrap_maps", action="store_true")                                        # build-side addition
     return parser
 
 
@@ -90,6 +106,10 @@ def parse_args(argv=None):
         given, other = ("--lpips_backbone", "--lpips_linear") if args.lpips_linear is None else \
             ("--lpips_linear", "--lpips_backbone")
         parser.error(f"{given} needs {other} as well: LPIPS takes both weight files or neither")
+    if args.bootstrap < 0 or args.bootstrap_batch < 1:
+        parser.error("--bootstrap takes a replica count >= 0 and --bootstrap_batch a chunk size >= 1")
+    if args.bootstrap_maps and args.out_dir is None:
+        parser.error("--bootstrap_maps needs --out_dir")
     return args
 
 
@@ -123,6 +143,14 @@ def main(argv=None):
     model.eval()
     if args.weights is not None:
         model.load_weights(get_weights(args.weights, args.device))
+
+    bootstrap = None
+    if args.bootstrap:                                        # (a folder of measurements: the physics is built for it alone)
+        from bootstrap import EquivariantBootstrap
+        boot_physics = physics if physics is not None else get_physics(args, device=args.device)
+        bootstrap = EquivariantBootstrap(boot_physics, lambda v: model(v.contiguous()), samples=args.bootstrap,
+                                         batch=args.bootstrap_batch)
+    est_list, q90_list = [], []
 
     lpips_net = None
     if args.lpips_backbone is not None:
@@ -171,6 +199,20 @@ def main(argv=None):
                 x_hat /= args.r2r_itercount
             else:
                 x_hat = model(y.contiguous())
+        if bootstrap is not None:
+            with fork_rng(enabled=True):                      # its draws leave the stream of the images that follow alone
+                torch.manual_seed(i)
+                boot = bootstrap(y.contiguous(), x_hat=x_hat)
+            est_list.append(boot["est_psnr"])
+            q90_list.append(boot["est_psnr_q90"])
+            if args.print_all_metrics:
+                print(f"BOOTSTRAP_{i}: EST_PSNR: {boot['est_psnr']:.2f}, EST_PSNR_Q90: {boot['est_psnr_q90']:.2f}")
+            if args.bootstrap_maps:
+                rmse = boot["rmse_map"]
+                stem = os.path.join(args.out_dir, "error_maps", os.path.splitext(basename_table.get(i, f"{i}.png"))[0])
+                os.makedirs(dirname(stem), exist_ok=True)
+                np.save(stem + ".npy", rmse.cpu().numpy())
+                save_image(rmse / rmse.max().clamp_min(1e-30), stem + ".png")
         x = quantize_and_clamp(x) if x is not None else None
         y = quantize_and_clamp(y)
         x_hat = quantize_and_clamp(x_hat)
@@ -201,6 +243,11 @@ def main(argv=None):
         print(f"SSIM std: {np.std(ssim_list):.4f}")
         print(f"LPIPS: {np.mean(lpips_list):.4f}")
         print(f"LPIPS std: {np.std(lpips_list):.4f}")
+    if est_list:
+        print(f"EST_N: {len(est_list)}")
+        print(f"EST_PSNR: {np.mean(est_list):.2f}")
+        print(f"EST_PSNR std: {np.std(est_list):.2f}")
+        print(f"EST_PSNR_Q90: {np.mean(q90_list):.2f}")
     return psnr_list
 
 
