@@ -927,6 +927,26 @@ int sei_gemm_bf16nt_dw2_adam_ex(const uint16_t *A1, const uint16_t *A2, int lda,
                                 int ldb, float *param, float *exp_avg, float *exp_avg_sq, uint16_t *param_bf16,
                                 const float *hyper, int M, int N, int K1, int K2, int tile, void *stream);
 size_t sei_gemm_bf16nt_dw2_adam_plan(int M, int N, int K1, int K2, int tile);
+/* Up to eight such GEMMs in ONE launch on the 128 x 256 tile (tile 16 above), one after the other (problem-major, every
+ * job's tiles in the order the job would take alone): the jobs' workgroups share the chip's slots, so one job's main loops
+ * run under another's parameter streams instead of every launch running all its loops and then all its epilogues. Per
+ * job the MFMA steps, their order and the Adam arithmetic are those of sei_gemm_bf16nt_dw2_adam_ex (tiles 1 and 16):
+ * every parameter, moment and bf16-copy bit is the same. One `hyper` serves all jobs. The table is copied into the
+ * launch's arguments: it need not outlive the call. SEI_ERR_BAD_ARG, with nothing launched: njobs outside
+ * 1..SEI_ADAM_GROUP_MAX_JOBS, a job that sei_gemm_bf16nt_dw2_adam_ex would refuse, M % 128 != 0 or N % 256 != 0, or two
+ * jobs whose state arrays overlap.
+ * sei_gemm_bf16nt_dw2_adam_groupable (host arithmetic): 1 = a problem the grouped launch takes AND gains from -- whole
+ * 128 x 256 tiles, and too few of them to run many rounds of workgroups on its own. */
+#define SEI_ADAM_GROUP_MAX_JOBS 8
+typedef struct SeiAdamGemmJob {
+    const uint16_t *A1, *A2;         /* (K1, lda) / (K2, lda) bf16, reduction-major as sei_gemm_bf16nt_dw2's */
+    const uint16_t *B1, *B2;         /* (K1, ldb) / (K2, ldb) */
+    float *param, *exp_avg, *exp_avg_sq;     /* (M, N), dense */
+    uint16_t *param_bf16;            /* NULL, or the bf16 copy of param */
+    int lda, ldb, M, N, K1, K2;
+} SeiAdamGemmJob;
+int sei_gemm_bf16nt_dw2_adam_group(const SeiAdamGemmJob *jobs, int njobs, const float *hyper, void *stream);
+size_t sei_gemm_bf16nt_dw2_adam_groupable(int M, int N, int K1, int K2);
 int sei_adam_scalars(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float *out6_host,
                      void *stream);
 /* the same values written to a DEVICE array by a launch on `stream` (what a training loop calls before every replay of

@@ -109,6 +109,7 @@ SIGNATURES = {
     "sei_gemm_bf16nt_dw2_ex": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "sei_gemm_bf16nt_dw2_adam": [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "sei_gemm_bf16nt_dw2_adam_ex": [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sei_gemm_bf16nt_dw2_adam_group": [_P, _I, _P, _P],
     "sei_gemm_bf16nt_dw2_bf16out": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P],
     "sei_gemm_bf16nt_dw2_taps": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P],
     "sei_sepmap2": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P],
@@ -203,6 +204,15 @@ class DwStreamJob(_c.Structure):
 DWSTREAM_MAX_JOBS = 64
 
 
+class AdamGemmJob(_c.Structure):
+    """SeiAdamGemmJob of include/sei_hip.h (one weight gradient of a sei_gemm_bf16nt_dw2_adam_group table)."""
+    _fields_ = [("A1", _P), ("A2", _P), ("B1", _P), ("B2", _P), ("param", _P), ("exp_avg", _P), ("exp_avg_sq", _P),
+                ("param_bf16", _P), ("lda", _I), ("ldb", _I), ("M", _I), ("N", _I), ("K1", _I), ("K2", _I)]
+
+
+ADAM_GROUP_MAX_JOBS = 8      # SEI_ADAM_GROUP_MAX_JOBS
+
+
 class FoldJob(_c.Structure):
     """SeiFoldJob of include/sei_hip.h (one destination of sei_fold_many with the partial sums of up to three launches)."""
     _fields_ = [("a", _P), ("b", _P), ("c", _P), ("ncol", _I), ("split", _I), ("kind", _I), ("nseg", _I),
@@ -257,6 +267,7 @@ SIZE_QUERIES = {
     "sei_gemm_bf16nt_plan": [_I, _I, _I, _I, _I, _I, _I, _I],
     "sei_gemm_bf16nt_plan_ws": [_I, _I, _I, _I, _I, _I, _I, _I, _Z],
     "sei_gemm_bf16nt_dw2_adam_plan": [_I, _I, _I, _I, _I],
+    "sei_gemm_bf16nt_dw2_adam_groupable": [_I, _I, _I, _I],
     "sei_conv3x3_bwd_weight_parts_count": [_I, _I, _I, _I, _I, _I, _I],
     "sei_sepmap2_small_eligible": [_I, _I, _I, _I, _I, _I],
     "sei_cast_bf16_colsum_parts_count": [_I, _I],
@@ -325,6 +336,11 @@ def adam_gemm_plan(M, Nn, K1, K2, tile=0):
     if code == 0:
         raise NativeLibraryError("sei_gemm_bf16nt_dw2_adam_plan: arguments sei_gemm_bf16nt_dw2_adam_ex would refuse")
     return {1: "nt", 2: "pq"}[code >> 48], (code >> 32) & 0xFFFF, (code >> 16) & 0xFFFF, code & 0x7FFF
+
+
+def adam_gemm_groupable(M, Nn, K1, K2):
+    """sei_gemm_bf16nt_dw2_adam_groupable: the grouped launch takes this weight gradient and gains from it (host arithmetic)."""
+    return lib().sei_gemm_bf16nt_dw2_adam_groupable(M, Nn, K1, K2) != 0
 
 
 def stream():

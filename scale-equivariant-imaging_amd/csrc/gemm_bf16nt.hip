@@ -24,6 +24,7 @@
 //   * gemm_bf16pp.h: an opt-in 256x256 ping-pong schedule on the same LDS images.
 //
 // Requirements checked by the host entries: K % 8 == 0, leading dimensions % 8 == 0, 16-byte aligned A and B.
+#include <climits>
 #include "rm_image.h"
 
 namespace {
@@ -91,6 +92,11 @@ struct NtArgs {
     void *ws = nullptr;
     size_t ws_bytes = 0;
     int force_splitk = 0;
+    // A group of weight-gradient GEMMs with the Adam epilogue in one launch (sei_gemm_bf16nt_dw2_adam_group, the ROWEPI == 6
+    // instantiation alone reads these): the caller's table by value, as batch_row travels -- a captured graph owns its
+    // copy -- and job_end[j] = the launch's blocks up to and including job j (INT_MAX past the last job).
+    int job_end[SEI_ADAM_GROUP_MAX_JOBS] = {};
+    SeiAdamGemmJob jobs[SEI_ADAM_GROUP_MAX_JOBS] = {};
 };
 
 __device__ __forceinline__ float4 nt_load4(const float *p) {
@@ -212,6 +218,39 @@ void gemm_bf16nt_kernel(NtArgs g) {
     // went from 78 to 102 VGPRs, i.e. from three workgroups per CU to two, with a run-time test here).
     const unsigned short *Bp = g.B, *B2p = g.B2;
     float *D32p = g.D32;
+    // ROWEPI == 6 marks the grouped instantiation (the Adam epilogue of ROWEPI == 1) in the same way: what a job of the
+    // table replaces is read through JOB_OR(local, argument), which IS the argument in every other instantiation.
+#define JOB_OR(local, field) (ROWEPI == 6 ? (local) : (g.field))
+#define J_TM JOB_OR(jtm, tiles_m)
+#define J_TN JOB_OR(jtn, tiles_n)
+#define J_TPX JOB_OR(jtpx, tiles_per_xcd)
+#define J_BAND JOB_OR(jband, band)
+#define J_LDA JOB_OR(jlda, lda)
+#define J_LDB JOB_OR(jldb, ldb)
+#define J_KSEG JOB_OR(jkseg, k_seg)
+#define J_A JOB_OR(jA, A)
+#define J_A2 JOB_OR(jA2, A2)
+    const unsigned short *jA = nullptr, *jA2 = nullptr;
+    float *jp = nullptr, *jm = nullptr, *jv = nullptr;
+    unsigned short *jp16 = nullptr;
+    int jM = 0, jN = 0, jK = 0, jlda = 0, jldb = 0, jkseg = 0, jtm = 0, jtn = 0, jtpx = 0, jband = 0;
+    if constexpr (ROWEPI == 6) {
+        // A group of whole problems in one launch (sei_gemm_bf16nt_dw2_adam_group): the blocks of job j are
+        // [job_end[j - 1], job_end[j]) -- problem-major, every job padded to whole rounds of the 8 XCDs, entries past the
+        // last job INT_MAX -- and inside a job the tiles keep the order the job would have alone. Everything here is
+        // uniform over the workgroup: the scan and the job's row of the table stay in scalar registers.
+        int j = 0;
+#pragma unroll
+        for (int t = 0; t < SEI_ADAM_GROUP_MAX_JOBS - 1; ++t) j += bid >= g.job_end[t] ? 1 : 0;
+        if (j > 0) bid -= g.job_end[j - 1];
+        const SeiAdamGemmJob &jb = g.jobs[j];
+        jA = jb.A1; jA2 = jb.A2; Bp = jb.B1; B2p = jb.B2;
+        jp = jb.param; jm = jb.exp_avg; jv = jb.exp_avg_sq; jp16 = jb.param_bf16;
+        jM = jb.M; jN = jb.N; jK = jb.K1 + jb.K2; jlda = jb.lda; jldb = jb.ldb; jkseg = jb.K1;
+        jtm = jM / (32 * TM * WM); jtn = jN / (32 * TN * WN);      // whole tiles only (the host entry refuses others)
+        jband = min(g.band, jtn);
+        jtpx = jtm * jtn < 64 ? 0 : (jtm * jtn + 7) >> 3;          // as launch_nt orders a job alone
+    }
     if constexpr (ROWEPI == 3) {
         const int per = gridDim.x / g.batch, bt = bid / per;
         bid -= bt * per;
@@ -221,29 +260,31 @@ void gemm_bf16nt_kernel(NtArgs g) {
         D32p += (size_t)bt * g.batch_ld;
     }
     int zs, ord;
-    if (g.tiles_per_xcd == 0) {
-        const int ntile = g.tiles_m * g.tiles_n;
+    if (J_TPX == 0) {
+        const int ntile = J_TM * J_TN;
         zs = bid / ntile;
         ord = bid - zs * ntile;
+        if constexpr (ROWEPI == 6)
+            if (zs > 0) return;                                    // a padding block; block-uniform, before any barrier
     } else {
-        const int per_split = 8 * g.tiles_per_xcd;
+        const int per_split = 8 * J_TPX;
         zs = bid / per_split;
         bid -= zs * per_split;
-        ord = (bid & 7) * g.tiles_per_xcd + (bid >> 3);
-        if ((bid >> 3) >= g.tiles_per_xcd || ord >= g.tiles_m * g.tiles_n) return;   // block-uniform, before any barrier
+        ord = (bid & 7) * J_TPX + (bid >> 3);
+        if ((bid >> 3) >= J_TPX || ord >= J_TM * J_TN) return;   // block-uniform, before any barrier
     }
     int tm_i, tn_i;
     {
-        const int band_tiles = g.tiles_m * g.band;
+        const int band_tiles = J_TM * J_BAND;
         const int b = ord / band_tiles, r = ord - b * band_tiles;
-        const int width = min(g.band, g.tiles_n - b * g.band);
+        const int width = min(J_BAND, J_TN - b * J_BAND);
         tm_i = r / width;
-        tn_i = b * g.band + (r - tm_i * width);
+        tn_i = b * J_BAND + (r - tm_i * width);
     }
     const int m0 = tm_i * BM, n0 = tn_i * BN;
-    const int M = g.M, N = g.N, K = g.K;
-    const int k_begin = zs * g.k_per_split;
-    const int k_end = min(K, k_begin + g.k_per_split);
+    const int M = JOB_OR(jM, M), N = JOB_OR(jN, N), K = JOB_OR(jK, K);
+    const int k_begin = zs * JOB_OR(jK, k_per_split);
+    const int k_end = min(K, k_begin + JOB_OR(jK, k_per_split));
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -311,10 +352,10 @@ void gemm_bf16nt_kernel(NtArgs g) {
         const int q = wave + NWAVES * e;
         if constexpr (ARM) {
             const int row = 4 * q + (lane >> 4), ch = (lane & 15) ^ swz_rmajor(row);
-            off_a[e] = (unsigned)row * (unsigned)g.lda * 2u + 2u * (unsigned)min(8 * ch, M - 8 - m0);
+            off_a[e] = (unsigned)row * (unsigned)J_LDA * 2u + 2u * (unsigned)min(8 * ch, M - 8 - m0);
         } else {
             const int row = 8 * q + (lane >> 3), c = (lane & 7) ^ ((row >> 1) & 7);
-            off_a[e] = (unsigned)min(row, M - 1 - m0) * (unsigned)g.lda * 2u + 16u * c;
+            off_a[e] = (unsigned)min(row, M - 1 - m0) * (unsigned)J_LDA * 2u + 16u * c;
         }
     }
 #pragma unroll
@@ -324,21 +365,21 @@ void gemm_bf16nt_kernel(NtArgs g) {
             constexpr int PPI = KS / 4;                        // 16 pieces per 128-column image (8 per half image)
             const int im = q / PPI, qq = q % PPI;
             const int row = 4 * qq + (lane >> 4), ch = (lane & 15) ^ swz_rmajor(row);
-            off_b[e] = (unsigned)row * (unsigned)g.ldb * 2u +
+            off_b[e] = (unsigned)row * (unsigned)J_LDB * 2u +
                        2u * (unsigned)max(min(128 * im + 8 * ch, N - 8 - n0), 0);
         } else {
             const int row = 8 * q + (lane >> 3), c = (lane & 7) ^ ((row >> 1) & 7);
-            off_b[e] = (unsigned)min(row, N - 1 - n0) * (unsigned)g.ldb * 2u + 16u * c;
+            off_b[e] = (unsigned)min(row, N - 1 - n0) * (unsigned)J_LDB * 2u + 16u * c;
         }
     }
     auto rm_base = [&](const unsigned short *X1, const unsigned short *X2, int ld, int o0, int k0) -> const char * {
-        if (k0 + KS <= g.k_seg && k0 + KS <= k_end) return reinterpret_cast<const char *>(X1 + (size_t)k0 * ld + o0);
-        if (k0 >= g.k_seg && k0 + KS <= k_end) return reinterpret_cast<const char *>(X2 + (size_t)(k0 - g.k_seg) * ld + o0);
+        if (k0 + KS <= J_KSEG && k0 + KS <= k_end) return reinterpret_cast<const char *>(X1 + (size_t)k0 * ld + o0);
+        if (k0 >= J_KSEG && k0 + KS <= k_end) return reinterpret_cast<const char *>(X2 + (size_t)(k0 - J_KSEG) * ld + o0);
         return nullptr;
     };
     auto stage = [&](int k0, char *dst) {
         const char *ab, *bb;
-        if constexpr (ARM) ab = rm_base(g.A, g.A2, g.lda, m0, k0);
+        if constexpr (ARM) ab = rm_base(J_A, J_A2, J_LDA, m0, k0);
         else if (g.conv_cin > 0) {                         // uniform per k-tile: the tap's row shift (K % BK == 0)
             const int tap = k0 / g.conv_cin;
             ab = reinterpret_cast<const char *>(g.A + ((ptrdiff_t)m0 + g.conv_off[tap]) * (ptrdiff_t)g.lda +
@@ -351,10 +392,10 @@ void gemm_bf16nt_kernel(NtArgs g) {
                 if (ARM || wave + NWAVES * e < BM / 8)         // wave-uniform (a 96-row tile has 12 pieces)
                     dma16_base(ab, off_a[e], dst + (wave + NWAVES * e) * 1024);
         } else {
-            if constexpr (ARM) stage_tile_rmajor<KS>(g.A, g.A2, g.k_seg, g.lda, m0, M, k0, k_end, dst, wave, lane);
+            if constexpr (ARM) stage_tile_rmajor<KS>(J_A, J_A2, J_KSEG, J_LDA, m0, M, k0, k_end, dst, wave, lane);
             else stage_tile<BM>(g.A, g.lda, m0, M, k0, k_end, dst, wave, lane);
         }
-        if constexpr (BRM) bb = rm_base(Bp, B2p, g.ldb, n0, k0);
+        if constexpr (BRM) bb = rm_base(Bp, B2p, J_LDB, n0, k0);
         else bb = k0 + BK <= k_end ? reinterpret_cast<const char *>(Bp + (size_t)n0 * g.ldb + k0) : nullptr;
         if (bb) {
 #pragma unroll
@@ -363,7 +404,7 @@ void gemm_bf16nt_kernel(NtArgs g) {
         } else if constexpr (BRM) {
 #pragma unroll
             for (int im = 0; im < BN / 128; ++im)           // 16 KB image per 128 columns
-                stage_tile_rmajor<KS>(Bp, B2p, g.k_seg, g.ldb, n0 + 128 * im, N, k0, k_end,
+                stage_tile_rmajor<KS>(Bp, B2p, J_KSEG, J_LDB, n0 + 128 * im, N, k0, k_end,
                                       dst + A_BYTES + im * IMG, wave, lane);
         } else {
             stage_tile<BN>(Bp, g.ldb, n0, N, k0, k_end, dst + A_BYTES, wave, lane);
@@ -484,7 +525,9 @@ void gemm_bf16nt_kernel(NtArgs g) {
         }
         return;
     }
-    if constexpr (ROWEPI == 1) {
+    if constexpr (ROWEPI == 1 || ROWEPI == 6) {                      // 6: the grouped launch, on its job's state
+        float *adam_p = JOB_OR(jp, adam_p), *adam_m = JOB_OR(jm, adam_m), *adam_v = JOB_OR(jv, adam_v);
+        unsigned short *adam_p16 = JOB_OR(jp16, adam_p16);
         static_assert(TM == 2 && (TN == 1 || TN == 2) && WM == 2 && WN == 4, "the row patch below is laid out for 128-row tiles");
         static_assert(64 * BN * 4 <= NSTAGE * STAGE, "half a tile of float32 fits the operand stages");
         constexpr int QSH = TN == 1 ? 5 : 6;                         // log2 of the quads in a patch row
@@ -523,9 +566,9 @@ void gemm_bf16nt_kernel(NtArgs g) {
                 off[k] = ok[k] ? (size_t)row * N + col : 0;
                 gq[k] = *reinterpret_cast<const float4 *>(patch + r * BN + 4 * c4);
                 // streamed once per step: non-temporal, so that they do not push the GEMM operands out of L2 / MALL
-                pq[k] = nt_load4(g.adam_p + off[k]);
-                mq[k] = nt_load4(g.adam_m + off[k]);
-                vq[k] = nt_load4(g.adam_v + off[k]);
+                pq[k] = nt_load4(adam_p + off[k]);
+                mq[k] = nt_load4(adam_m + off[k]);
+                vq[k] = nt_load4(adam_v + off[k]);
             }
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -535,16 +578,16 @@ void gemm_bf16nt_kernel(NtArgs g) {
                 o.y = sei_adam_element(pq[k].y, gq[k].y, mq[k].y, vq[k].y, beta1, beta2, eps, wd, step_size, inv_bc2_sqrt);
                 o.z = sei_adam_element(pq[k].z, gq[k].z, mq[k].z, vq[k].z, beta1, beta2, eps, wd, step_size, inv_bc2_sqrt);
                 o.w = sei_adam_element(pq[k].w, gq[k].w, mq[k].w, vq[k].w, beta1, beta2, eps, wd, step_size, inv_bc2_sqrt);
-                nt_store4(g.adam_m + off[k], mq[k]);
-                nt_store4(g.adam_v + off[k], vq[k]);
-                nt_store4(g.adam_p + off[k], o);
-                if (g.adam_p16) {
+                nt_store4(adam_m + off[k], mq[k]);
+                nt_store4(adam_v + off[k], vq[k]);
+                nt_store4(adam_p + off[k], o);
+                if (adam_p16) {
                     uint2 w;
                     w.x = sei_pack2_bf16(o.x, o.y);
                     w.y = sei_pack2_bf16(o.z, o.w);
                     u32x2 t;
                     t.x = w.x; t.y = w.y;
-                    __builtin_nontemporal_store(t, reinterpret_cast<u32x2 *>(g.adam_p16 + off[k]));
+                    __builtin_nontemporal_store(t, reinterpret_cast<u32x2 *>(adam_p16 + off[k]));
                 }
             }
           }
@@ -712,6 +755,16 @@ void gemm_bf16nt_kernel(NtArgs g) {
 
 // Zero-fill of a split-K output. A kernel (not hipMemsetAsync): a memset issued from inside the library was
 // observed not to be replayed reliably as part of a captured hipGraph, which left stale partial sums.
+#undef JOB_OR
+#undef J_TM
+#undef J_TN
+#undef J_TPX
+#undef J_BAND
+#undef J_LDA
+#undef J_LDB
+#undef J_KSEG
+#undef J_A
+#undef J_A2
 __global__ __launch_bounds__(256) void zero_fill_kernel(float *__restrict__ p, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t n4 = n / 4;
@@ -942,7 +995,9 @@ int pq_choose_rr(const NtArgs &g) {
 // tools/exp_adam_stagger.py, 2048 x 8192 x 3456 184 -> 188 ... 210 us, 8192 x 32768 x 864 1409 -> 1412 ... 1434. The main loop
 // of a 128 x 128 tile moves 1.77 MB of operands through the CU's global -> LDS path against the epilogue's 0.43 MB. That
 // path is what bounds the main loop -- the 128 x 256 tile below moves 3/4 of the bytes and its loop runs 1.3 - 1.5 times
-// faster -- but NOT the epilogue: that one is HBM's, and cut out of the launch it takes as long on either tile.)
+// faster -- but NOT the epilogue: that one is HBM's, and cut out of the launch it takes as long on either tile. What does
+// break the lockstep of a one-round launch is more rounds: sei_gemm_bf16nt_dw2_adam_group below issues several such
+// problems as one launch, adam_groupable says which.)
 bool pq_adam_auto(const NtArgs &) { return false; }
 
 // The 128 x 256 tile of the same loop (launch_nt<2, 2, 2, 4, true, true, 3, 1>): per output element a workgroup stages
@@ -959,11 +1014,21 @@ bool pq_adam_auto(const NtArgs &) { return false; }
 // ~98 us + epilogue ~88 us = the launch. Whole tiles only, enough of them to
 // fill the 2 x 256 workgroup slots of the chip in every round, and a long reduction or many rounds.
 bool adam_wide_fits(const NtArgs &g) { return g.M % 128 == 0 && g.N % 256 == 0; }
+// (the pair's rule: at least 8 rounds of the chip's 512 slots. Over that many rounds the workgroups drift out of phase by
+// themselves, the main loops run under other workgroups' epilogues and the launch takes the epilogue's time.)
+constexpr size_t ADAM_WIDE_MANY_ROUNDS_TILES = 4096;
 bool adam_wide_auto(const NtArgs &g) {
     if (!adam_wide_fits(g)) return false;
     const size_t tiles = (size_t)(g.M / 128) * (size_t)(g.N / 256);
     if (tiles < 512 || (double)tiles / (double)(sei_ceil_div(tiles, 512) * 512) < 0.8) return false;
-    return g.K >= 2048 || tiles >= 4096;
+    return g.K >= 2048 || tiles >= ADAM_WIDE_MANY_ROUNDS_TILES;
+}
+// What sei_gemm_bf16nt_dw2_adam_group is FOR: a problem of whole wide tiles that alone runs fewer rounds than the pair's
+// rule asks -- level 3's launches are ONE round, all main loops (the CU's global -> LDS path, HBM idle) and then all
+// epilogues (HBM, the matrix cores idle). Several of them in one launch are what the pair is: rounds whose loops hide under
+// the epilogues of the round before. A problem of many rounds has nothing left to hide and stays a launch of its own.
+bool adam_groupable(const NtArgs &g) {
+    return adam_wide_fits(g) && (size_t)(g.M / 128) * (size_t)(g.N / 256) < ADAM_WIDE_MANY_ROUNDS_TILES;
 }
 // Tile order of the wide tile: bands of 8 tile columns (the XCD's 64 tiles in flight = 8 x 8 tiles, 1024 rows x 2048 columns,
 // 8 KB of every parameter row at a time) instead of launch_nt's square patch in elements (6). Measured, us, bands of
@@ -1354,6 +1419,55 @@ extern "C" int sei_gemm_bf16nt_dw2_adam(const uint16_t *A1, const uint16_t *A2, 
                                         void *stream) {
     return sei_gemm_bf16nt_dw2_adam_ex(A1, A2, lda, B1, B2, ldb, param, exp_avg, exp_avg_sq, param_bf16, hyper, M, N, K1, K2,
                                        0, stream);
+}
+
+// Several weight-gradient GEMMs with the Adam epilogue as ONE launch of the wide tile (adam_groupable says why): the job
+// table travels in the argument block, the blocks of job j follow those of job j - 1.
+extern "C" int sei_gemm_bf16nt_dw2_adam_group(const SeiAdamGemmJob *jobs, int njobs, const float *hyper, void *stream) {
+    SEI_REQUIRE(jobs && hyper && njobs >= 1 && njobs <= SEI_ADAM_GROUP_MAX_JOBS);
+    NtArgs g;
+    struct Range { uintptr_t lo, hi; };
+    Range state[SEI_ADAM_GROUP_MAX_JOBS][4];
+    size_t blocks = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const SeiAdamGemmJob &jb = jobs[j];
+        NtArgs one;                                             // checked as the job's own launch would be
+        SEI_REQUIRE(jb.param && jb.exp_avg && jb.exp_avg_sq &&
+                    nt_fill_dw2(one, jb.A1, jb.A2, jb.lda, jb.B1, jb.B2, jb.ldb, jb.M, jb.N, jb.K1, jb.K2, 1) == SEI_OK);
+        SEI_REQUIRE((((uintptr_t)jb.param | (uintptr_t)jb.exp_avg | (uintptr_t)jb.exp_avg_sq) & 15) == 0 &&
+                    ((uintptr_t)jb.param_bf16 & 7) == 0);       // the epilogue moves whole quads
+        SEI_REQUIRE(adam_wide_fits(one));
+        const size_t n = (size_t)jb.M * jb.N, tiles = (size_t)(jb.M / 128) * (size_t)(jb.N / 256);
+        SEI_REQUIRE(tiles < ((size_t)1 << 24));
+        // every job writes its state while the others run: no two jobs may share a byte of it
+        const void *base[4] = {jb.param, jb.exp_avg, jb.exp_avg_sq, jb.param_bf16};
+        for (int a = 0; a < 4; ++a) {
+            const uintptr_t lo = (uintptr_t)base[a];
+            state[j][a] = {lo, base[a] ? lo + n * (a == 3 ? 2 : 4) : lo};
+            for (int i = 0; i < j; ++i)
+                for (int b = 0; b < 4; ++b)
+                    SEI_REQUIRE(!(state[j][a].lo < state[i][b].hi && state[i][b].lo < state[j][a].hi));
+        }
+        blocks += 8 * sei_ceil_div(tiles, 8);                   // whole rounds of the 8 XCDs: the order a job has alone
+        g.jobs[j] = jb;
+        g.job_end[j] = (int)blocks;
+    }
+    for (int j = njobs; j < SEI_ADAM_GROUP_MAX_JOBS; ++j) g.job_end[j] = INT_MAX;
+    SEI_REQUIRE(blocks < ((size_t)1 << 27));
+    g.adam_h = hyper;
+    g.epilogue = SEI_EPI_NONE;
+    g.splitk = 1;
+    g.band = ADAM_WIDE_BAND;
+    hipLaunchKernelGGL((gemm_bf16nt_kernel<2, 2, 2, 4, true, true, 3, 6>), dim3((unsigned)blocks), dim3(NT), 0,
+                       (hipStream_t)stream, g);
+    return sei_launch_status();
+}
+
+extern "C" size_t sei_gemm_bf16nt_dw2_adam_groupable(int M, int N, int K1, int K2) {
+    const uint16_t *fake16 = reinterpret_cast<const uint16_t *>(uintptr_t(1) << 20);      // never dereferenced
+    NtArgs g;
+    if (nt_fill_dw2(g, fake16, fake16, M, fake16, fake16, N, M, N, K1, K2, 1) != SEI_OK) return 0;
+    return adam_groupable(g) ? 1 : 0;
 }
 
 extern "C" int sei_gemm_bf16nt_dw2_bf16out(const uint16_t *A1, const uint16_t *A2, int lda, const uint16_t *B1,

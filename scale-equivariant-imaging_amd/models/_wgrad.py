@@ -43,7 +43,22 @@ SINK_ADAM, SINK_BF16 = "adam", "direct16"
 _SINKS = {SINK_ADAM: ("sei_gemm_bf16nt_dw2_adam", "fused optimizer step"),
           SINK_BF16: ("sei_gemm_bf16nt_dw2_bf16out", "bf16 gradients written into the exchange buffer")}
 
+# Grouped fused-Adam launches. A SINK_ADAM weight gradient of whole 128 x 256 tiles that alone runs a single round of
+# workgroups (N.adam_gemm_groupable: the rule lives in csrc/gemm_bf16nt.hip beside adam_wide_auto) is not launched where it
+# arrives but queued, operands kept alive, and the queue goes out as ONE sei_gemm_bf16nt_dw2_adam_group launch per <= 8
+# jobs when the backward pass ends: the main loops of one job then run under the parameter streams of another, where a
+# launch of its own runs all its loops and then all its epilogues. Deferring is safe because
+#   * a weight's bf16 copy is read in the backward pass only by its own layer's data-gradient GEMMs, and every layer
+#     function issues those BEFORE it hands in the weight gradient (models/_ops.py, ConvBlockFn16.backward);
+#   * nothing between the arrival and the end of the backward pass reads the parameter, its moments or its copy: the
+#     optimizer's own pass, the shadow refresh and the next forward all follow the engine callback;
+#   * SINK_ADAM is registered only without a reducer (graphs.GraphedLossStep._plan_sinks), and while a milestone is set
+#     (early release) nothing is queued: the event never waits for a deferred launch.
+# Outside a backward pass nothing is deferred. SEI_NO_ADAM_GROUP=1: every launch where it arrives, as before.
+ADAM_GROUP = os.environ.get("SEI_NO_ADAM_GROUP") != "1"
+
 _Queued = collections.namedtuple("_Queued", "job operands grad flops")     # one entry of WeightGradState.dwjobs
+_QueuedAdam = collections.namedtuple("_QueuedAdam", "job operands hyper flops args")   # one of WeightGradState.adamjobs
 
 
 def _segments(pairs):
@@ -119,7 +134,7 @@ class WeightGradState:
     registered range (kernel-level tests) share the default state. Gradients are known by their data_ptr (`key`)."""
 
     __slots__ = ("uses", "records", "parked", "store", "store_min", "merge", "flush_queued", "milestone", "milestone_done",
-                 "dwjobs", "folds", "__weakref__")
+                 "dwjobs", "adamjobs", "folds", "__weakref__")
 
     def __init__(self):
         self.uses = 0                   # differentiated model calls of this step (note_forward)
@@ -130,6 +145,7 @@ class WeightGradState:
         self.flush_queued = False       # the engine callback of the running backward pass is queued
         self.milestone, self.milestone_done = None, False   # (frozenset of keys, event) or None (set_weight_grad_milestone)
         self.dwjobs = []                # [_Queued] for the streamed launch; their operands live until it is issued
+        self.adamjobs = []              # [_QueuedAdam] for the grouped fused-Adam launch; operands live until it is issued
         self.folds = {}                 # destination pointer -> {"meta", "segs"}: deferred folds of the running pass
 
     def record(self, key, shape, tapped=False):
@@ -150,6 +166,8 @@ class WeightGradState:
         for rec in self.records.values():
             if rec.sink is not None and rec.sink[0] == kind:
                 rec.sink, rec.sink_launched = None, False
+        if kind == SINK_ADAM:
+            self.adamjobs = []          # (left behind only by a step that raised: their registration ends here)
         for key, views in (table or {}).items():
             rec = self.record(key, views[0].shape)
             rec.sink, rec.sink_launched = (kind, views), False
@@ -212,7 +230,9 @@ class WeightGradState:
                 raise RuntimeError(f"{what}: a registered weight did not receive its gradient as one merged storing GEMM "
                                    "(different loss / batch / call count than planned)")
             rec.sink_launched = True
-            _gemm_call(2.0 * Np * Kp * (K1 + K2), entry, *operands, *[N.ptr(v) for v in views], Np, Kp, K1, K2)
+            args = (*operands, *[N.ptr(v) for v in views], Np, Kp, K1, K2)
+            if kind != SINK_ADAM or not self.queue_adam_group((g1, x1, g2, x2), views, args):
+                _gemm_call(2.0 * Np * Kp * (K1 + K2), entry, *args)
             return
         taps = rec.taps
         if taps is not None:                               # (T, N', K') gradient: every tap in one launch
@@ -325,6 +345,33 @@ class WeightGradState:
         arr = (N.DwStreamJob * len(jobs))(*[q.job for q in jobs])
         _gemm_call(sum(q.flops for q in jobs), "sei_dwstream_bf16_jobs", arr, len(jobs))   # (`jobs` kept the operands alive)
 
+    # -- grouped fused-Adam launches (ADAM_GROUP above) -----------------------------------------------------
+    def queue_adam_group(self, operands, views, args):
+        """Queue the fused-Adam launch with the ungrouped arguments `args` for the grouped launch; False: launch it now."""
+        Np, Kp, K1, K2 = args[-4:]
+        if not ADAM_GROUP or self.milestone is not None or not N.adam_gemm_groupable(Np, Kp, K1, K2):
+            return False
+        hyper = views[-1]
+        if self.adamjobs and self.adamjobs[0].hyper is not hyper:      # one array of step scalars per launch
+            self.flush_adam_group()
+        if not self.queue_flush():
+            return False
+        g1, x1, g2, x2 = operands
+        job = N.AdamGemmJob(g1.data_ptr(), g2.data_ptr(), x1.data_ptr(), x2.data_ptr(), *[N.ptr(v) for v in views[:4]],
+                            Np, Kp, Np, Kp, K1, K2)
+        self.adamjobs.append(_QueuedAdam(job, operands, hyper, 2.0 * Np * Kp * (K1 + K2), args))
+        return True
+
+    def flush_adam_group(self):
+        jobs, self.adamjobs = self.adamjobs, []
+        for i in range(0, len(jobs), N.ADAM_GROUP_MAX_JOBS):
+            chunk = jobs[i:i + N.ADAM_GROUP_MAX_JOBS]               # (`jobs` keeps the operands alive until here)
+            if len(chunk) == 1:
+                _gemm_call(chunk[0].flops, _SINKS[SINK_ADAM][0], *chunk[0].args)
+                continue
+            arr = (N.AdamGemmJob * len(chunk))(*[q.job for q in chunk])
+            _gemm_call(sum(q.flops for q in chunk), "sei_gemm_bf16nt_dw2_adam_group", arr, len(chunk), N.ptr(chunk[0].hyper))
+
     # -- deferred folds (DEFERRED_FOLDS above) --------------------------------------------------------------
     def defer_fold(self, a, b, c, ncol, split, kind, work, offset, groups):
         if not self.queue_flush():
@@ -368,7 +415,8 @@ class WeightGradState:
         return True
 
     def flush(self):
-        """Issue every parked weight gradient on its own (no partner arrived), then the streamed jobs and the folds."""
+        """Issue every parked weight gradient on its own (no partner arrived), then the streamed jobs, the grouped fused-Adam
+        launch and the folds."""
         self.flush_queued = False
         parked, self.parked = self.parked, {}
         for entry in parked.values():
@@ -377,6 +425,7 @@ class WeightGradState:
             else:
                 self.launch(entry[2], [entry[:2]])
         self.flush_dwstream()
+        self.flush_adam_group()
         self.flush_folds()
 
 
