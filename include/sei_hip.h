@@ -339,6 +339,35 @@ size_t sei_boot_luma_diff_work_floats(int batch, size_t npix);
 int sei_boot_pullback_accum(const float *d, const float *rate, const float *center, int B, int H, int W, float *msq,
                             int accumulate, void *stream);
 
+/* Noise levels from measurements alone (csrc/noise_est_kernels.hip, noise_estimation.py; DESIGN 4.20: the project's own
+ * definition, no parity with a published estimator is claimed). The operators here are blurs and antialiased downsamplings,
+ * so the diagonal Haar detail of y is almost pure noise. Constants: L = 64 intensity levels, K = 256 magnitude bins, lattice
+ * 510, c = 0.6744897501960817 (the median of |N(0, 1)|), LEVEL_LO = 6, LEVEL_HI = 57, N_MIN = 256.
+ *   sei_noise_quad_hist: for every non-overlapping 2 x 2 quad (a b / c d) of every plane of the float32 (planes, H, W) tensor
+ *     y, top-left corner at an even row and an even column (a trailing odd row or column is ignored), in float32, unfused,
+ *     in this order:
+ *       s = ((a + b) + (c + d)) * 0.25f,   t = ((a - b) - (c - d)) * 0.5f;
+ *       the quad counts only if all four pixels satisfy 0 < p < 1 (clipped and non-finite pixels are dropped);
+ *       l = clamp((int)floorf(s * 64.f), 0, 63),   k = min(255, (int)floorf(fabsf(t) * 510.f + 0.5f)), product and sum rounded
+ *       separately (bins one 8-bit half-step wide, centred on the lattice of quantised images; bin 255 takes the overflow);
+ *       hist[l][k] += 1.
+ *     hist: L x K unsigned 64-bit counters in device memory, 8-byte aligned. accumulate = 0 zeroes them first, on the stream;
+ *     otherwise calls add up, so a folder pools into one histogram. Integer counts: independent of the order of the atomics,
+ *     bit-reproducible. y: 4-byte aligned; a 16-byte aligned y with W % 4 == 0 takes the float4 path, the same counts.
+ *   sei_noise_fit: out8 = (sigma, eta, gamma, levels_used, quads_counted, flags, 0, 0) in double precision, sequential loops
+ *     in index order. Interpolated median med(h) of a K-bin row with total n: half = n / 2, j = the first bin whose inclusive
+ *     prefix sum is >= half, below = the prefix sum before j, lo = max(j - 0.5, 0), hi = j + 0.5,
+ *     med = (lo + (hi - lo) * (half - below) / h[j]) / 510. sigma = med(sum over l of hist[l]) / c. Level l is used when
+ *     LEVEL_LO <= l <= LEVEL_HI, its total n_l >= N_MIN and its median bin is not 255; v_l = (med(hist[l]) / c)^2,
+ *     m_l = (l + 0.5) / 64, weight w_l = n_l. (eta, gamma): the weighted least-squares line v = eta + gamma m from the centred
+ *     sums (mbar = sum w m / sum w, vbar likewise, gamma = sum w (m - mbar)(v - vbar) / sum w (m - mbar)^2,
+ *     eta = vbar - gamma mbar). Flags: 1 an empty histogram (sigma, eta, gamma NaN; the counts 0); 2 the pooled median is in
+ *     bin 255 (sigma NaN); 4 fewer than two used levels or no spread of m (gamma = 0, eta = sigma^2); 8 gamma < 0 (gamma = 0,
+ *     eta = vbar); 16 eta < 0 (eta = 0, gamma = sum w m v / sum w m^2).
+ * SEI_ERR_BAD_ARG on NULL pointers, planes < 1, H < 2, W < 2 or H * W >= 2^30; nothing is launched then. */
+int sei_noise_quad_hist(const float *y, int planes, int H, int W, unsigned long long *hist, int accumulate, void *stream);
+int sei_noise_fit(const unsigned long long *hist, double *out8, void *stream);
+
 /* LPIPS v0.1 on AlexNet features (csrc/lpips_kernels.hip; reference src/metrics.py: pyiqa.create_metric("lpips")), float32.
  * For an H x W RGB image in [0, 1] (H, W >= 31: below that the second pool has nothing to work on):
  *   v = ((2 x - 1) - shift) / scale per channel, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450);

@@ -46,6 +46,15 @@ physics of --task / --kernel / --sr_factor / --noise_level is built for the boot
 writes error_maps/NAME.npy (float32 root-mean-square error per pixel) and NAME.png (the same over its own maximum): a
 qualitative picture of where the errors sit. Calibration of EST_PSNR against the true PSNR is not shown in this build (no
 trained weights); on a dataset with ground truth both are printed side by side.
+`--estimate_noise gaussian | poisson_gaussian` (build-side addition; noise_estimation.py, the sei_noise_* kernels: the
+project's own estimator) reads the noise levels off the measurements themselves: `NOISE_i: SIGMA_255, ETA, GAIN`
+per image under --print_all_metrics and `EST_NOISE_N`, `EST_SIGMA_255`, `EST_ETA`, `EST_GAIN` at the end, pooled over every
+processed measurement through one accumulated histogram (variance = ETA + GAIN * signal; SIGMA_255 is the Gaussian level on
+--noise_level's scale). It draws no random numbers: every other line is what it is without the flag. With a folder of
+measurements and --bootstrap, the whole folder is estimated first and the bootstrap's physics gets the estimated level
+(gaussian: sigma; poisson_gaussian: sqrt(eta) and the gain, or sigma with a notice when the two-level fit did not hold)
+in place of --noise_level / --noise_gain, which nobody knows for measured data; one line says which levels it used. On a
+dataset with ground truth the flag only prints: the synthetic physics keeps its flags.
 """
 import os
 import sys
@@ -96,6 +105,7 @@ def build_parser():
     flag("--bootstrap", type=int, default=0, metavar="N")                                # build-side addition
     flag("--bootstrap_batch", type=int, default=8, metavar="B")                          # build-side addition
     flag("--bootstrap_maps", action="store_true")                                        # build-side addition
+    flag("--estimate_noise", choices=["gaussian", "poisson_gaussian"], default=None)     # build-side addition
     return parser
 
 
@@ -167,6 +177,22 @@ def main(argv=None):
     else:
         dataset = get_dataset(args=args, purpose="test", physics=physics, device=args.device, _HOTFIX=False)
 
+    noise_pooled, noise_count = None, 0
+    if args.estimate_noise is not None:
+        from noise_estimation import NoiseEstimator, bootstrap_levels
+        from physics import GaussianNoise, PoissonGaussianNoise
+        noise_pooled, noise_single = NoiseEstimator(args.device), NoiseEstimator(args.device)
+        if bootstrap is not None and physics is None:         # measured data: nobody knows --noise_level / --noise_gain
+            for _, y in dataset:
+                noise_single.add(y)
+            sigma, gain, notice = bootstrap_levels(noise_single.estimate(), args.estimate_noise)
+            if notice is not None:
+                print(f"BOOTSTRAP_NOISE: {notice}")
+            boot_physics.noise_model = PoissonGaussianNoise(sigma=sigma, gain=gain) if gain > 0 else \
+                GaussianNoise(sigma=sigma)
+            print(f"BOOTSTRAP_NOISE: the bootstrap measures again with SIGMA_255: {255 * sigma:.3f}, GAIN: {gain:.5f} "
+                  f"(--estimate_noise {args.estimate_noise} over {len(dataset)} measurements)")
+
     if args.save_psf:
         assert args.out_dir is not None
         assert physics.task == "deblurring"
@@ -182,6 +208,12 @@ def main(argv=None):
         x, y = dataset[i]
         x = x.unsqueeze(0) if x is not None else None
         y = y.unsqueeze(0)
+        if noise_pooled is not None:
+            noise_pooled.add(y)
+            noise_count += 1
+            if args.print_all_metrics:
+                one = noise_single.reset().add(y).estimate()
+                print(f"NOISE_{i}: SIGMA_255: {one['sigma_255']:.3f}, ETA: {one['eta']:.3e}, GAIN: {one['gain']:.5f}")
         with torch.no_grad():
             if args.noise2inverse:                            # reference demo/test.py:116-126
                 from noise2inverse import Noise2InverseModel
@@ -248,6 +280,12 @@ def main(argv=None):
         print(f"EST_PSNR: {np.mean(est_list):.2f}")
         print(f"EST_PSNR std: {np.std(est_list):.2f}")
         print(f"EST_PSNR_Q90: {np.mean(q90_list):.2f}")
+    if noise_count:
+        pooled = noise_pooled.estimate()
+        print(f"EST_NOISE_N: {noise_count}")
+        print(f"EST_SIGMA_255: {pooled['sigma_255']:.3f}")
+        print(f"EST_ETA: {pooled['eta']:.3e}")
+        print(f"EST_GAIN: {pooled['gain']:.5f}")
     return psnr_list
 
 

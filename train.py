@@ -36,6 +36,8 @@ step runs in libsei_hip.so. Differences, all build-side and documented in DESIGN
     signal) instead: a second multiplier started from `--unsure_init_gain` and moved by `--unsure_gain_step_size`, a fourth
     csv column `Estimated Noise Gain`, eight floats in `loss_state`. `--noise_gain G` (settings.py) makes the synthetic
     measurements Poisson-Gaussian.
+    `--unsure_init_from_measurements` (with a folder `--dataset DIR`): the multipliers start from the levels that
+    noise_estimation.py reads off the loaded crops (the sei_noise_* kernels) instead of from a guess.
 """
 import csv
 import os
@@ -132,6 +134,9 @@ def build_parser():
          help="starting guess of the gain, in image units with images in [0, 1] (--unsure_noise_model poisson_gaussian)")
     flag("--unsure_gain_step_size", type=float, default=None,
          help="ascent step of the gain's multiplier (default: --unsure_step_size)")
+    flag("--unsure_init_from_measurements", default=False, **onoff,
+         help="start the multipliers of --sure_unknown_noise from the noise levels estimated on the measurements of the "
+              "folder --dataset DIR (noise_estimation.py) instead of --unsure_init_noise_level / --unsure_init_gain")
     flag("--device_cache", default=False, **onoff,
          help="keep every (x, y) training pair in HBM (deterministic measurements) and draw crops on the device "
               "instead of the per-item DataLoader path (datasets/device_cache.py)")
@@ -156,6 +161,52 @@ def check_fine_tuning_args(args):
         raise ValueError(f"--fine_tuning_params trains {FINE_TUNING_PARAMS[0]} and {FINE_TUNING_PARAMS[1]}: only "
                          "--ProposedModel__architecture Transformer has a conv_last, not "
                          f"{args.ProposedModel__architecture}")
+
+
+UNSURE_FROM_FLAG = "--unsure_init_from_measurements"
+
+
+def check_unsure_init_args(args):
+    """What --unsure_init_from_measurements needs, refused by the flag's name before any GPU object exists."""
+    if not args.unsure_init_from_measurements:
+        return
+    if not args.sure_unknown_noise:
+        raise ValueError(f"{UNSURE_FROM_FLAG} starts the multipliers of --sure_unknown_noise: pass --sure_unknown_noise as well")
+    if args.dataset is None or not isdir(args.dataset):
+        raise ValueError(f"{UNSURE_FROM_FLAG} estimates the levels on measured data: --dataset must be a folder of PNG "
+                         f"measurements, not {args.dataset!r} (synthetic measurements are made at --noise_level)")
+    if args.unsure_init_noise_level is not None or args.unsure_init_gain != 0:
+        raise ValueError(f"{UNSURE_FROM_FLAG} cannot be combined with an explicit --unsure_init_noise_level or "
+                         "--unsure_init_gain: the start is either estimated or given")
+    if args.RESUME is not None:
+        raise ValueError(f"{UNSURE_FROM_FLAG} cannot be combined with --RESUME: a resumed run starts from the checkpoint's "
+                         "loss_state")
+
+
+def init_unsure_from_measurements(unsure, pairs, poisson_gaussian):
+    """Estimate the noise levels over the loaded crops and write them into the UNSURE term's device state in place (a
+    captured step reads the buffer's address): sigma^2, or eta and the gain."""
+    from noise_estimation import NoiseEstimator
+    estimator = NoiseEstimator(unsure.noise_state.device)
+    for _, y in pairs:
+        estimator.add(y)
+    est = estimator.estimate()
+    if not np.isfinite(est["sigma"]):
+        raise ValueError(f"{UNSURE_FROM_FLAG}: no noise level could be read off the measurements (flags {est['flags']})")
+    eta, gain = est["sigma"] ** 2, 0.0
+    if poisson_gaussian:
+        if est["model_ok"]:
+            eta, gain = est["eta"], est["gain"]
+        else:
+            print(f"\n{UNSURE_FROM_FLAG}: the Poisson-Gaussian fit did not hold (flags {est['flags']}, "
+                  f"{est['levels_used']} levels): starting from the Gaussian level and a gain of 0\n")
+    with torch.no_grad():
+        unsure.noise_state[0] = eta
+        if poisson_gaussian:
+            unsure.noise_state[4] = gain
+    print(f"\nUNSURE starts from the measurements ({est['quads']} quads of {len(pairs)} crops): noise level "
+          f"{255 * eta ** 0.5:.3f}" + (f", gain {gain:.5f}" if poisson_gaussian else "") + "\n")
+    return est
 
 
 def _crop_offsets(height, width, size):
@@ -199,6 +250,7 @@ def main(argv=None):
         torch.cuda.set_device(args.device)
     check_fine_tuning_args(args)
     check_unsure_args(args, world)
+    check_unsure_init_args(args)
     crop.FIX_BATCHED_CROP = args.fix_batched_crop
 
     physics = get_physics(args, device=args.device)
@@ -219,6 +271,8 @@ def main(argv=None):
         unsure.to(args.device)
     if isdir(args.dataset):
         dataset = measurement_folder(args.dataset, args.PrepareTrainingPairs__crop_size, args.device)
+        if args.unsure_init_from_measurements:
+            init_unsure_from_measurements(unsure, dataset, unsure_pg)
     else:
         dataset = get_dataset(args=args, purpose="train", physics=physics, device=args.device,
                               _HOTFIX=(args.task == "sr"))
