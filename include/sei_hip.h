@@ -368,6 +368,38 @@ int sei_boot_pullback_accum(const float *d, const float *rate, const float *cent
 int sei_noise_quad_hist(const float *y, int planes, int H, int W, unsigned long long *hist, int accumulate, void *stream);
 int sei_noise_fit(const unsigned long long *hist, double *out8, void *stream);
 
+/* Tiled inference (csrc/tile_kernels.hip, tiling.py, test.py --tile): one (C, H, W) image is cut into
+ * overlapping tiles, a model runs on batches of them, and the tiles it returns are blended into one image. The plan of an
+ * axis of length n with tile T and overlap v, 0 <= 2 v <= T: n <= T gives one tile of extent Te = n at origin 0; otherwise
+ * Te = T, the stride is s = T - v, and the origins are 0, s, 2s, ... strictly below n - T followed by n - T (the last tile is
+ * shifted back to end on the border; nothing is padded). Tiles are the product grid of the two axes, t = ty * nx + tx.
+ * Origins are not passed: they follow from (H, Th, sy, ny) as o_k = k * sy for k < ny - 1 and o_last = H - Th, and the overlap
+ * is Th - sy (on a single-tile axis it only caps the feather window). All extents are in pixels of the tensors of the call:
+ * a plan multiplied by an integer is the plan of the multiplied image, which is how the output of an SR model is blended.
+ * Window weight of position i inside a tile of extent Te at origin o, an integer:
+ *   window 0 (uniform): 1;   window 1 (feather): min(i + 1, Te - i, max(v, 1));
+ *   window 2 (crop): 1 if lo <= i < Te - hi, else 0, with lo = 0 if o == 0 else v / 2, hi = 0 if o + Te == n else v - v / 2
+ *   (integer division: each pixel comes from tiles that see at least v / 2 pixels of context around it).
+ *   sei_tile_gather: tiles[t - t0] = x[:, oy : oy + Th, ox : ox + Tw] for t = t0 .. t0 + n - 1, a contiguous (n, C, Th, Tw)
+ *     batch; a bit-for-bit copy.
+ *   sei_tile_blend: out[c, y, x] = (sum over the tiles t0 .. t0 + n - 1 that cover (y, x), in ascending t, of
+ *     wy * wx * tiles[t - t0][c, y - oy, x - ox]) / (Sy(y) * Sx(x)), Sy and Sx the per-axis sums of the weights over every tile
+ *     of the plan. The sum is acc = fmaf(w, value, acc), w = (float)(wy * wx) (exact: Th, Tw <= 2048), from 0 when
+ *     accumulate == 0 and from the numerators already in out otherwise; a tile whose weight at a pixel is 0 is not read there.
+ *     finish != 0 divides (correctly rounded, as sei_boot_luma_diff divides). Calls over consecutive chunks of tiles, the later
+ *     ones with accumulate != 0 and the last with finish != 0, leave the bits of one call over all tiles: gather form, a thread
+ *     owns output pixels and finds their at most 3 x 3 covering tiles arithmetically; no atomics.
+ * Pointers are 4-byte aligned; 16-byte accesses are used wherever four floats of a row sit on the 16-byte grid, scalar ones
+ * elsewhere, with the same bits. SEI_ERR_BAD_ARG, with nothing launched, on NULL or misaligned pointers, non-positive extents
+ * or C, Th or Tw above 2048, a stride above its tile, 2 (Th - sy) > Th where ny > 1 (likewise x), a (H, Th, sy, ny) that is not
+ * the plan above (ny == 1 needs Th == H; otherwise (ny - 2) sy < H - Th <= (ny - 1) sy; likewise x), window outside 0 .. 2,
+ * t0 < 0, n < 1, t0 + n > ny * nx, 2^30 pixels or more per plane, 2^31 (tile, channel) planes or more in the chunk, or an image
+ * that overlaps the tile batch. */
+int sei_tile_gather(const float *x, float *tiles, int C, int H, int W, int Th, int Tw, int sy, int sx, int ny, int nx,
+                    int t0, int n, void *stream);
+int sei_tile_blend(const float *tiles, float *out, int C, int H, int W, int Th, int Tw, int sy, int sx, int ny, int nx,
+                   int window, int t0, int n, int accumulate, int finish, void *stream);
+
 /* LPIPS v0.1 on AlexNet features (csrc/lpips_kernels.hip; reference src/metrics.py: pyiqa.create_metric("lpips")), float32.
  * For an H x W RGB image in [0, 1] (H, W >= 31: below that the second pool has nothing to work on):
  *   v = ((2 x - 1) - shift) / scale per channel, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450);

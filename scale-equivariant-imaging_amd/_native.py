@@ -62,6 +62,8 @@ SIGNATURES = {
     "sei_boot_pullback_accum": [_P, _P, _P, _I, _I, _I, _P, _I, _P],
     "sei_noise_quad_hist": [_P, _I, _I, _I, _P, _I, _P],
     "sei_noise_fit": [_P, _P, _P],
+    "sei_tile_gather": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sei_tile_blend": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sei_lpips_conv_relu": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "sei_lpips_maxpool": [_P, _P, _I, _I, _I, _I, _P],
     "sei_lpips_layer_dist": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P],

@@ -55,6 +55,13 @@ measurements and --bootstrap, the whole folder is estimated first and the bootst
 (gaussian: sigma; poisson_gaussian: sqrt(eta) and the gain, or sigma with a notice when the two-level fit did not hold)
 in place of --noise_level / --noise_gain, which nobody knows for measured data; one line says which levels it used. On a
 dataset with ground truth the flag only prints: the synthetic physics keeps its flags.
+`--tile T [--tile_overlap V] [--tile_batch B] [--tile_window feather | uniform | crop]` (build-side addition; tiling.py, the
+sei_tile_* kernels) reconstructs every image from overlapping T x T tiles (T a multiple of 16 up to 2048,
+2 V <= T, default V = 32), B tiles per model call, blended under the window: frames of any size at the memory of a tile.
+Every model call of this driver then goes through one tiling.TiledModel: the plain path, the --noise2inverse backbone, the
+--r2r loop and the bootstrap's replicas. Feed-forward kinds only (Proposed, Identity, Upsample); for the networks of this
+build tiling is an approximation whose seams the overlap hides, not the whole-image result. Without the flag every call and
+every printed line is what it was.
 """
 import os
 import sys
@@ -106,6 +113,10 @@ def build_parser():
     flag("--bootstrap_batch", type=int, default=8, metavar="B")                          # build-side addition
     flag("--bootstrap_maps", action="store_true")                                        # build-side addition
     flag("--estimate_noise", choices=["gaussian", "poisson_gaussian"], default=None)     # build-side addition
+    flag("--tile", type=int, default=0, metavar="T")                                     # build-side addition
+    flag("--tile_overlap", type=int, default=32, metavar="V")                            # build-side addition
+    flag("--tile_batch", type=int, default=8, metavar="B")                               # build-side addition
+    flag("--tile_window", choices=["feather", "uniform", "crop"], default="feather")     # build-side addition
     return parser
 
 
@@ -120,7 +131,34 @@ def parse_args(argv=None):
         parser.error("--bootstrap takes a replica count >= 0 and --bootstrap_batch a chunk size >= 1")
     if args.bootstrap_maps and args.out_dir is None:
         parser.error("--bootstrap_maps needs --out_dir")
+    if args.tile < 0 or args.tile % 16 != 0 or args.tile > 2048:
+        parser.error("--tile takes a multiple of 16 up to 2048 (neither SwinIR's window of 8 nor the U-Net's 2^4 then pads "
+                     "a full tile; 0 switches tiling off)")
+    if args.tile_overlap < 0 or (args.tile and 2 * args.tile_overlap > args.tile):
+        parser.error("--tile_overlap takes an overlap V >= 0 with 2 V <= --tile")
+    if args.tile_batch < 1:
+        parser.error("--tile_batch takes a chunk size >= 1")
+    if args.tile and args.model_kind not in TILED_KINDS:
+        parser.error(f"--tile runs feed-forward model kinds only ({', '.join(TILED_KINDS)}): --model_kind {args.model_kind} "
+                     "carries the physics at the whole image's extents inside the model, and tiling it would be a different "
+                     "algorithm")
+    if args.tile and tile_scale(args) * args.tile > 2048:
+        parser.error(f"--tile times the super-resolution factor {tile_scale(args)} must stay within 2048 output pixels")
     return args
+
+
+TILED_KINDS = ("Proposed", "Identity", "Upsample")
+
+
+def tile_scale(args):
+    """The integer by which the model multiplies the extents of its input: the physics' rate for a Proposed SR model,
+    --sr_factor for the bicubic Upsample kind whatever the task, 1 otherwise (also for the homogeneous SwinIR of
+    models/__init__.py, which maps measurements already brought to the ground truth's size)."""
+    if args.model_kind == "Proposed" and args.ProposedModel__architecture == "Transformer" and "HOMOGENEOUS_SWINIR" in os.environ:
+        return 1
+    if args.model_kind == "Upsample" or (args.model_kind == "Proposed" and args.task == "sr"):
+        return int(args.sr_factor or 1)
+    return 1
 
 
 def quantize_and_clamp(im):
@@ -154,11 +192,17 @@ def main(argv=None):
     if args.weights is not None:
         model.load_weights(get_weights(args.weights, args.device))
 
+    forward = model                                           # every model call below goes through it
+    if args.tile:
+        from tiling import TiledModel
+        forward = TiledModel(model, tile=args.tile, overlap=args.tile_overlap, batch=args.tile_batch,
+                             scale=tile_scale(args), window=args.tile_window)
+
     bootstrap = None
     if args.bootstrap:                                        # (a folder of measurements: the physics is built for it alone)
         from bootstrap import EquivariantBootstrap
         boot_physics = physics if physics is not None else get_physics(args, device=args.device)
-        bootstrap = EquivariantBootstrap(boot_physics, lambda v: model(v.contiguous()), samples=args.bootstrap,
+        bootstrap = EquivariantBootstrap(boot_physics, lambda v: forward(v.contiguous()), samples=args.bootstrap,
                                          batch=args.bootstrap_batch)
     est_list, q90_list = [], []
 
@@ -219,7 +263,7 @@ def main(argv=None):
                 from noise2inverse import Noise2InverseModel
                 if physics.task != "deblurring" and not hasattr(physics, "A_dagger"):
                     raise NotImplementedError("--noise2inverse needs physics.A_dagger outside deblurring")
-                wrapped = Noise2InverseModel(backbone=lambda v: model(v.contiguous()), task=physics.task,
+                wrapped = Noise2InverseModel(backbone=lambda v: forward(v.contiguous()), task=physics.task,
                                              physics_filter=getattr(physics, "filter", None),
                                              degradation_inverse_fn=getattr(physics, "A_dagger", None))
                 x_hat = wrapped(y)
@@ -227,10 +271,10 @@ def main(argv=None):
                 x_hat = torch.zeros_like(x)
                 for _ in range(args.r2r_itercount):
                     pert = torch.randn_like(y) * physics.noise_model.sigma
-                    x_hat += model((y + 0.5 * pert).contiguous())
+                    x_hat += forward((y + 0.5 * pert).contiguous())
                 x_hat /= args.r2r_itercount
             else:
-                x_hat = model(y.contiguous())
+                x_hat = forward(y.contiguous())
         if bootstrap is not None:
             with fork_rng(enabled=True):                      # its draws leave the stream of the images that follow alone
                 torch.manual_seed(i)
