@@ -2,7 +2,7 @@
 // residual blocks with timestep scale-shift, biased 3x3 convolutions at 128 .. 1024 input channels, blocks that resample
 // inside, and global self-attention with 64-wide heads.
 //
-// Layout: DRUNet's (csrc/drunet_kernels.hip). The trunk and every convolution result are float32 channels-last on the row
+// Layout: that of csrc/grid_conv.h. The trunk and every convolution result are float32 channels-last on the row
 // indexing of a zero-bordered grid (B, H + 2, W + 2, C), R = B (H + 2) (W + 2) rows; the input of a convolution is a bf16
 // grid of the same rows with W + 3 guard rows in front and behind; weights are bf16, tap-major (N, taps * Cin),
 // K-contiguous. Every kernel reads and writes INTERIOR rows only (the packed image grid excepted, which is written whole):
@@ -16,15 +16,13 @@
 //                         as the bf16 grid of the next convolution and / or as float32, at the same extents, 2x2-averaged
 //                         into the half extents or repeated 2x into the double ones; without statistics it is the plain
 //                         copy / resampling of the residual path R(x) (and the bf16 copy the 1x1 skip convolution reads).
-//   adm_conv_kernel       DRUNet's implicit GEMM (one wave: 16 pb grid rows x 64 channels, fragments straight from global
-//                         memory, two reduction steps in flight) with any Cin that is a multiple of 32 (384 and 768 have 12
-//                         and 24 steps per tap, no power of two), 9 taps or 1, and the epilogue (acc + bias) [+ residual] ->
-//                         float32 and / or bf16; the tail writes 3 channels of an NCHW image. No split-K, no atomics: an
-//                         output element is one wave's k-ordered MFMA chain, the same bits on every run and batch position.
+//   adm_conv_kernel       the implicit GEMM of grid_conv.h with any Cin that is a multiple of 32 (384 and 768 have 12 and 24
+//                         steps per tap, no power of two), 9 taps or 1, and the epilogue (acc + bias) [+ residual] -> float32
+//                         and / or bf16; the tail writes 3 channels of an NCHW image.
 //   adm_attention_kernel  softmax((q^T k) / 8) v per head over all T = H W tokens of an image, flash style: one wave per 16
 //                         queries walks the keys in tiles of 32, scores and the output on bf16 MFMA, the running row maximum
 //                         and sum in float32, the probabilities rounded to bf16 for the second product.
-#include "sei_common.h"
+#include "grid_conv.h"
 
 #include <math.h>
 
@@ -32,13 +30,6 @@ namespace {
 
 constexpr int ADM_GROUPS = 32;
 
-bool adm_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-// rows of the zero-bordered grid of B images of H x W, 0 when the arguments are refused (or the row count leaves int)
-long long adm_rows(int B, int H, int W) {
-    if (B < 1 || H < 1 || W < 1 || H > 16384 || W > 16384) return 0;
-    const long long r = (long long)B * (H + 2) * (W + 2);
-    return r < (1ll << 30) ? r : 0;
-}
 bool adm_channels(int Ca, int Cb) {          // the concatenation has whole groups of a multiple of 4 channels
     return Ca >= 4 && Cb >= 0 && Ca % 4 == 0 && Cb % 4 == 0 && (Ca + Cb) % (4 * ADM_GROUPS) == 0 && Ca + Cb <= 4096;
 }
@@ -193,25 +184,6 @@ __global__ __launch_bounds__(256) void adm_gn_apply_kernel(const AdmApply a) {
     }
 }
 
-// x (B, 3, H, W) float32 -> the head's input grid: 32 channels (x, zeros) per row, border rows zero
-constexpr int ADM_HEAD_CIN = 32;
-__global__ void adm_pack_image_kernel(const float *x, uint16_t *g, int B, int H, int W) {
-    const int Hp = H + 2, Wp = W + 2;
-    const size_t n = (size_t)B * Hp * Wp * (ADM_HEAD_CIN / 8);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int chunk = (int)(i % (ADM_HEAD_CIN / 8));
-        const size_t r = i / (ADM_HEAD_CIN / 8);
-        const int j = (int)(r % Wp), q = (int)(r / Wp), ii = q % Hp, b = q / Hp;
-        u32x4 v{0u, 0u, 0u, 0u};
-        if (chunk == 0 && ii >= 1 && ii <= H && j >= 1 && j <= W) {
-            const size_t plane = (size_t)H * W, at = (size_t)b * 3 * plane + (size_t)(ii - 1) * W + (j - 1);
-            v[0] = sei_pack2_bf16(x[at], x[at + plane]);
-            v[1] = sei_pack2_bf16(x[at + 2 * plane], 0.f);
-        }
-        *reinterpret_cast<u32x4 *>(g + r * ADM_HEAD_CIN + 8 * chunk) = v;
-    }
-}
-
 // ---- the convolution ----
 enum { ADM_EPI_TRUNK = 0, ADM_EPI_TAIL = 1 };
 struct AdmConv {
@@ -226,101 +198,28 @@ struct AdmConv {
     int Cout;                                // the tail: channels of the image
 };
 
-// One wave per workgroup: PB 16-row blocks of grid rows x NB 16-channel blocks; the reduction runs in steps of 32 channels
-// of one tap, Cin / 32 steps per tap (any count: the tap of a step comes from a multiply and a shift, exact below 2^20 / spt
-// steps), three register sets as in drunet_gemm_kernel.
+// grid_conv with any count of steps per tap (Cin / 32) and the family's epilogue
 template <int NB, int PB, int EPI>
 __global__ __launch_bounds__(64) void adm_conv_kernel(const AdmConv a) {
-    const int lane = threadIdx.x, l16 = lane & 15, lg = lane >> 4;
-    const int m0 = blockIdx.x * (16 * PB), n0 = blockIdx.y * (16 * NB);
-    const int Hp = a.H + 2, Wp = a.W + 2;
-    int mrow[PB], bi[PB], ii[PB], jj[PB];
-    bool ok[PB];
-    const uint16_t *xb[PB], *wb[NB];
-#pragma unroll
-    for (int p = 0; p < PB; ++p) {
-        const int m = m0 + 16 * p + l16;
-        mrow[p] = min(m, a.M - 1);           // rows past the end read the last row and store nothing
-        jj[p] = mrow[p] % Wp;
-        const int q = mrow[p] / Wp;
-        ii[p] = q % Hp;
-        bi[p] = q / Hp;
-        ok[p] = m < a.M && ii[p] >= 1 && ii[p] <= a.H && jj[p] >= 1 && jj[p] <= a.W;
-        xb[p] = a.X + (long long)mrow[p] * a.Cin + 8 * lg;
-    }
-    const size_t K = (size_t)a.ntaps * a.Cin;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) wb[j] = a.Wt + (size_t)(n0 + 16 * j + l16) * K + 8 * lg;
-
-    f32x4 acc[NB][PB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int p = 0; p < PB; ++p) acc[j][p] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const unsigned spt = (unsigned)a.Cin >> 5, inv = ((1u << 20) + spt - 1) / spt;
-    const int total = a.ntaps * (int)spt;
-    auto load = [&](int s, bf16x8(&fx)[PB], bf16x8(&fw)[NB]) {
-        const int t = (int)(((unsigned)s * inv) >> 20), c0 = (s - t * (int)spt) << 5;          // wave-uniform
-        const int shift = a.ntaps == 1 ? 0 : (t / 3 - 1) * Wp + (t % 3 - 1);                   // grid rows to tap t
-        const long long off = (long long)shift * a.Cin + c0;
-#pragma unroll
-        for (int p = 0; p < PB; ++p) fx[p] = *reinterpret_cast<const bf16x8 *>(xb[p] + off);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) fw[j] = *reinterpret_cast<const bf16x8 *>(wb[j] + (size_t)s * 32);
-    };
-    auto mma = [&](const bf16x8(&fx)[PB], const bf16x8(&fw)[NB]) {
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int p = 0; p < PB; ++p) acc[j][p] = sei_mfma16(fw[j], fx[p], acc[j][p]);
-    };
-    bf16x8 x0[PB], x1[PB], x2[PB], w0[NB], w1[NB], w2[NB];
-    const int last = total - 1;
-    load(0, x0, w0);
-    load(min(1, last), x1, w1);
-    for (int s = 0; s < total; s += 3) {
-        load(min(s + 2, last), x2, w2);
-        mma(x0, w0);
-        if (s + 1 >= total) break;
-        load(min(s + 3, last), x0, w0);
-        mma(x1, w1);
-        if (s + 2 >= total) break;
-        load(min(s + 4, last), x1, w1);
-        mma(x2, w2);
-    }
-
-    // accumulator element e of block (j, p): channel n0 + 16 j + 4 lg + e of grid row m0 + 16 p + l16
-#pragma unroll
-    for (int p = 0; p < PB; ++p) {
-        if (!ok[p]) continue;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int n = n0 + 16 * j + 4 * lg;
-            f32x4 v = acc[j][p] + *reinterpret_cast<const f32x4 *>(a.bias + n);
-            if (EPI == ADM_EPI_TRUNK) {
-                const size_t at = (size_t)mrow[p] * a.N + n;
-                if (a.Tres) v = v + *reinterpret_cast<const f32x4 *>(a.Tres + at);
-                if (a.Tout) *reinterpret_cast<f32x4 *>(a.Tout + at) = v;
-                if (a.Y16)
-                    *reinterpret_cast<u32x2 *>(a.Y16 + at) = u32x2{sei_pack2_bf16(v[0], v[1]), sei_pack2_bf16(v[2], v[3])};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (n + e < a.Cout)
-                        a.Tout[(((size_t)bi[p] * a.Cout + n + e) * a.H + (ii[p] - 1)) * a.W + (jj[p] - 1)] = v[e];
-            }
+    const GridConv core{a.X, a.Wt, a.Cin, a.ntaps, a.N, a.M, a.H, a.W};
+    grid_conv<NB, PB, false, false>(core, [&](const GridRow &r, int n, f32x4 acc) {
+        f32x4 v = acc + *reinterpret_cast<const f32x4 *>(a.bias + n);
+        if (EPI == ADM_EPI_TRUNK) {
+            const size_t at = (size_t)r.row * a.N + n;
+            if (a.Tres) v = v + *reinterpret_cast<const f32x4 *>(a.Tres + at);
+            if (a.Tout) *reinterpret_cast<f32x4 *>(a.Tout + at) = v;
+            if (a.Y16) *reinterpret_cast<u32x2 *>(a.Y16 + at) = u32x2{sei_pack2_bf16(v[0], v[1]), sei_pack2_bf16(v[2], v[3])};
+        } else {
+            grid_store_nchw(a.Tout, a.Cout, a.H, a.W, r, n, v);
         }
-    }
+    });
 }
 
 template <int NB, int EPI>
 int adm_conv_launch(const AdmConv &a, hipStream_t s) {
-    // rows per wave: DRUNet's measured rule (drunet_kernels.hip) -- 64 where that leaves 320 waves, else 32
-    const bool wide = (long long)sei_ceil_div((size_t)a.M, 64) * (a.N / (16 * NB)) >= 320;
-    const dim3 grid((unsigned)sei_ceil_div((size_t)a.M, wide ? 64 : 32), (unsigned)(a.N / (16 * NB)));
-    if (wide) hipLaunchKernelGGL((adm_conv_kernel<NB, 4, EPI>), grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((adm_conv_kernel<NB, 2, EPI>), grid, dim3(64), 0, s, a);
+    if (grid_default_pb(a.M, a.N, NB) == 4)
+        hipLaunchKernelGGL((adm_conv_kernel<NB, 4, EPI>), (grid_conv_waves<NB, 4>(a.M, a.N)), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((adm_conv_kernel<NB, 2, EPI>), (grid_conv_waves<NB, 2>(a.M, a.N)), dim3(64), 0, s, a);
     return sei_launch_status();
 }
 
@@ -405,14 +304,14 @@ __global__ __launch_bounds__(64) void adm_attention_kernel(const uint16_t *QKV, 
 }  // namespace
 
 extern "C" size_t sei_adm_gn_part_floats(int H, int W) {
-    return adm_rows(1, H, W) ? (size_t)2 * ADM_GROUPS * adm_gn_slices(H, W) : 0;
+    return grid_rows(1, H, W) ? (size_t)2 * ADM_GROUPS * adm_gn_slices(H, W) : 0;
 }
 
 extern "C" int sei_adm_gn_stats(const float *Xa, int Ca, const float *Xb, int Cb, int B, int H, int W, float eps, float *stats,
                                 float *part, void *stream) {
-    SEI_REQUIRE(Xa && stats && part && adm_al16(Xa) && adm_al16(Xb) && ((uintptr_t)stats & 3) == 0 && ((uintptr_t)part & 3) == 0);
+    SEI_REQUIRE(Xa && stats && part && grid_al16(Xa) && grid_al16(Xb) && ((uintptr_t)stats & 3) == 0 && ((uintptr_t)part & 3) == 0);
     SEI_REQUIRE(adm_channels(Ca, Cb) && (Cb == 0) == (Xb == nullptr) && eps > 0.f);
-    SEI_REQUIRE(adm_rows(B, H, W) > 0 && B <= 65535);
+    SEI_REQUIRE(grid_rows(B, H, W) > 0 && B <= 65535);
     const int slices = adm_gn_slices(H, W);
     SEI_REQUIRE(slices <= 65535);
     hipLaunchKernelGGL(adm_gn_stats_kernel, dim3(ADM_GROUPS, B, slices), dim3(ADM_GN_THREADS), 0, (hipStream_t)stream,
@@ -426,15 +325,15 @@ extern "C" int sei_adm_gn_stats(const float *Xa, int Ca, const float *Xb, int Cb
 extern "C" int sei_adm_gn_apply(const float *Xa, int Ca, const float *Xb, int Cb, const float *stats, const float *gamma,
                                 const float *beta, const float *mod, int silu, int B, int H, int W, int resample,
                                 uint16_t *Y16, float *Y32, void *stream) {
-    SEI_REQUIRE(Xa && (Y16 || Y32) && adm_al16(Xa) && adm_al16(Xb) && adm_al16(Y16) && adm_al16(Y32));
+    SEI_REQUIRE(Xa && (Y16 || Y32) && grid_al16(Xa) && grid_al16(Xb) && grid_al16(Y16) && grid_al16(Y32));
     SEI_REQUIRE(adm_channels(Ca, Cb) && (Cb == 0) == (Xb == nullptr));
     SEI_REQUIRE(Y32 != Xa && (!Xb || Y32 != Xb));
-    if (stats) SEI_REQUIRE(gamma && beta && adm_al16(gamma) && adm_al16(beta) && adm_al16(mod) && ((uintptr_t)stats & 3) == 0);
+    if (stats) SEI_REQUIRE(gamma && beta && grid_al16(gamma) && grid_al16(beta) && grid_al16(mod) && ((uintptr_t)stats & 3) == 0);
     else SEI_REQUIRE(!gamma && !beta && !mod);
     SEI_REQUIRE((resample == ADM_SAME || resample == ADM_DOWN || resample == ADM_UP) && (silu == 0 || silu == 1));
-    SEI_REQUIRE(adm_rows(B, H, W) > 0);
+    SEI_REQUIRE(grid_rows(B, H, W) > 0);
     if (resample == ADM_DOWN) SEI_REQUIRE(H % 2 == 0 && W % 2 == 0);
-    if (resample == ADM_UP) SEI_REQUIRE(adm_rows(B, 2 * H, 2 * W) > 0);
+    if (resample == ADM_UP) SEI_REQUIRE(grid_rows(B, 2 * H, 2 * W) > 0);
     const int Ho = resample == ADM_DOWN ? H / 2 : resample == ADM_UP ? 2 * H : H;
     const int Wo = resample == ADM_DOWN ? W / 2 : resample == ADM_UP ? 2 * W : W;
     const size_t items = (size_t)B * Ho * Wo * ((Ca + Cb) / 4);
@@ -444,21 +343,20 @@ extern "C" int sei_adm_gn_apply(const float *Xa, int Ca, const float *Xb, int Cb
 }
 
 extern "C" int sei_adm_pack_image(const float *x, uint16_t *G16, int B, int H, int W, void *stream) {
-    SEI_REQUIRE(x && G16 && ((uintptr_t)x & 3) == 0 && adm_al16(G16));
-    const long long R = adm_rows(B, H, W);
+    SEI_REQUIRE(x && G16 && ((uintptr_t)x & 3) == 0 && grid_al16(G16));
+    const long long R = grid_rows(B, H, W);
     SEI_REQUIRE(R > 0);
-    hipLaunchKernelGGL(adm_pack_image_kernel, dim3(sei_capped_grid((size_t)R * (ADM_HEAD_CIN / 8), 256, 4096)), dim3(256), 0,
-                       (hipStream_t)stream, x, G16, B, H, W);
+    grid_pack_image(x, 0.f, G16, R, B, H, W, (hipStream_t)stream);          // channel 3: zero like the rest
     return sei_launch_status();
 }
 
 extern "C" int sei_adm_conv(const uint16_t *X, const uint16_t *Wt, const float *bias, int Cin, int Cout, int ntaps, int B, int H,
                             int W, const float *T_res, float *T_out, uint16_t *Y16, void *stream) {
-    SEI_REQUIRE(X && Wt && bias && (T_out || Y16) && X != Y16 && adm_al16(X) && adm_al16(Wt) && adm_al16(bias) &&
-                adm_al16(T_res) && adm_al16(T_out) && adm_al16(Y16));
+    SEI_REQUIRE(X && Wt && bias && (T_out || Y16) && X != Y16 && grid_al16(X) && grid_al16(Wt) && grid_al16(bias) &&
+                grid_al16(T_res) && grid_al16(T_out) && grid_al16(Y16));
     SEI_REQUIRE(Cin >= 32 && Cin % 32 == 0 && Cin <= 4096 && Cout >= 64 && Cout % 64 == 0 && Cout <= 8192);
     SEI_REQUIRE(ntaps == 1 || ntaps == 9);
-    const long long R = adm_rows(B, H, W);
+    const long long R = grid_rows(B, H, W);
     SEI_REQUIRE(R > 0);
     AdmConv a{X, Wt, bias, T_res, T_out, Y16, Cin, ntaps, Cout, (int)R, H, W, Cout};
     return adm_conv_launch<4, ADM_EPI_TRUNK>(a, (hipStream_t)stream);
@@ -466,18 +364,18 @@ extern "C" int sei_adm_conv(const uint16_t *X, const uint16_t *Wt, const float *
 
 extern "C" int sei_adm_tail(const uint16_t *X, const uint16_t *Wt, const float *bias, int Cin, int B, int H, int W, float *out,
                             void *stream) {
-    SEI_REQUIRE(X && Wt && bias && out && adm_al16(X) && adm_al16(Wt) && adm_al16(bias) && ((uintptr_t)out & 3) == 0);
+    SEI_REQUIRE(X && Wt && bias && out && grid_al16(X) && grid_al16(Wt) && grid_al16(bias) && ((uintptr_t)out & 3) == 0);
     SEI_REQUIRE(Cin >= 32 && Cin % 32 == 0 && Cin <= 4096);
-    const long long R = adm_rows(B, H, W);
+    const long long R = grid_rows(B, H, W);
     SEI_REQUIRE(R > 0);
     AdmConv a{X, Wt, bias, nullptr, out, nullptr, Cin, 9, 16, (int)R, H, W, 3};
     return adm_conv_launch<1, ADM_EPI_TAIL>(a, (hipStream_t)stream);
 }
 
 extern "C" int sei_adm_attention(const uint16_t *QKV16, int C, int B, int H, int W, uint16_t *A16, void *stream) {
-    SEI_REQUIRE(QKV16 && A16 && adm_al16(QKV16) && adm_al16(A16));
+    SEI_REQUIRE(QKV16 && A16 && grid_al16(QKV16) && grid_al16(A16));
     SEI_REQUIRE(C >= ADM_HEAD_DIM && C % ADM_HEAD_DIM == 0 && C <= 4096);
-    SEI_REQUIRE(adm_rows(B, H, W) > 0 && B <= 65535 && (long long)H * W <= (1 << 20));
+    SEI_REQUIRE(grid_rows(B, H, W) > 0 && B <= 65535 && (long long)H * W <= (1 << 20));
     const dim3 grid((unsigned)sei_ceil_div((size_t)H * W, 16), (unsigned)(C / ADM_HEAD_DIM), (unsigned)B);
     hipLaunchKernelGGL(adm_attention_kernel, grid, dim3(64), 0, (hipStream_t)stream, QKV16, A16, C, H, W);
     return sei_launch_status();

@@ -2,8 +2,9 @@
 """One denoiser call of the diffusion U-Net (models/diffunet.py, the DiffPIR_DiffUNet baseline's network) at 1 x 256 x 256
 and 1 x 512 x 512: device time per kernel family of the "bf16" mode (sei_adm_*) and end to end, beside the float32
 composition of the parity mode and DRUNet's call (models/drunet.py) at the same extents; and each (C, C) 3x3 convolution for
-C in 128, 256, 512 beside sei_drunet_conv3x3 at the same extents in the same run -- the yardstick: the same implicit-GEMM
-body should not be slower there.
+C in 128, 256, 512 beside sei_drunet_conv3x3 at the same extents in the same run -- the yardstick: both are the grid_conv
+body of csrc/grid_conv.h, so what separates the two columns is the tap index of a non-power-of-two step count, the bias and
+the epilogue's traffic.
 
     python tools/exp_diffunet.py [--csv OUT.csv]
 
