@@ -55,7 +55,7 @@ extern "C" {
 
 /* ABI version of this header; sei_abi_version() returns the value the library was built with. Adding an entry point
  * is backward compatible and does not change it: sei_circ_filter_sep, sei_blur_sep_circ_lds, sei_resample_sepband_lds,
- * sei_blur_dense_pad, sei_blur_dense_pad_work_floats and the sei_bm3d_* family joined version 12 that way (a binding written against an earlier 12 keeps working; one that needs a new symbol checks
+ * sei_blur_dense_pad, sei_blur_dense_pad_work_floats, sei_blur_decimate (+ _work_floats) and the sei_bm3d_* family joined version 12 that way (a binding written against an earlier 12 keeps working; one that needs a new symbol checks
  * for it by name). */
 #define SEI_ABI_VERSION 12
 int sei_abi_version(void);
@@ -118,6 +118,30 @@ int sei_blur_dense_circ(const float *x, float *y, const float *k, int kv, int kh
 int sei_blur_dense_pad(const float *x, float *y, const float *k, int kv, int kh, int planes, int H, int W, int mode,
                        int transpose, float *work, void *stream);
 size_t sei_blur_dense_pad_work_floats(int planes, int H, int W, int kv, int kh, int mode, int transpose);
+
+/* INTERNAL (joined version 12 as an addition). The classical super-resolution degradation, blur then decimation, as one
+ * operator (physics/blur_downsampling.py; no counterpart in the reference, whose src/physics/__init__.py:11 asks for it):
+ * the blur above sampled at (phase_v :: rate, phase_h :: rate), evaluating the kept samples only. k is (kv,kh) row-major,
+ * H x W the IMAGE's extents in both directions, rate 1..8, phases in [0, rate) and below the extent of their axis.
+ * mode: 0 circular (the rule of sei_blur_dense_circ: map(e) = e mod n, S = K/2), 1 replicate, 2 reflect (the rules of
+ * sei_blur_dense_pad: (S, p) as there; reflect needs p <= n-1). 3, valid, is SEI_ERR_BAD_ARG: the image is then not rate
+ * times the measurement. Per axis of length n, n_out = (n - phase + rate - 1) / rate:
+ *   transpose = 0   y[i'] = sum_a c[a] x[map(rate i' + phase - a + S)],   i' in [0, n_out);   x (planes,H,W), y (planes,
+ *                   n_out_v, n_out_h). With rate 1 this is the blur itself.
+ *   transpose = 1   the exact transpose: x is the measurement-sized image, y is H x W,
+ *                   out[u] = sum over (i', a) with map(rate i' + phase - a + S) == u of c[a] x[i'].
+ * A gather in a fixed order, no atomics: the same bits on every run. Each pixel visits only the taps whose residue mod
+ * rate reaches it. Replicate / reflect: the zero-boundary correlation on the canvas extended by p goes to `work`, then the
+ * fold of sei_blur_dense_pad (two launches). Circular: one launch, the wraps are folded in the kernel, whatever their
+ * number (kernels larger than the image included); work may be NULL.
+ * sei_blur_decimate_work_floats: the floats `work` must hold: planes (H + 2pv) (W + 2ph) for the transposes of replicate
+ * and reflect, 0 otherwise -- and 0 for arguments the entry point refuses (the phases are taken as 0).
+ * Taps <= 63 per axis (SEI_ERR_TOO_LARGE beyond). No launch asks for more than 64 KiB of LDS: the forward tile (16 x 32
+ * measurement pixels) is halved until its footprint, (tile - 1) rate + K per axis, fits. SEI_ERR_BAD_ARG on NULL pointers,
+ * on a rate or phase outside its range, and when y or work overlap another operand; all before any launch. */
+int sei_blur_decimate(const float *x, float *y, const float *k, int kv, int kh, int planes, int H, int W, int mode,
+                      int rate, int phase_v, int phase_h, int transpose, float *work, void *stream);
+size_t sei_blur_decimate_work_floats(int planes, int H, int W, int kv, int kh, int mode, int rate, int transpose);
 
 /* ---------------------------------------------------------------------------------------------
  * Physics: separable dense circular filter  y[p] = C_v * x[p] * C_h^T  with full circulants

@@ -32,6 +32,7 @@ SIGNATURES = {
     "sei_blur_sep_circ": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sei_blur_dense_circ": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sei_blur_dense_pad": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "sei_blur_decimate": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "sei_circ_filter_sep": [_P, _P, _P, _P, _I, _I, _I, _P],
     "sei_resample_sepband": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P],
     "sei_scale_params": [_P, _P, _P, _I, _I, _P, _P, _P],
@@ -241,6 +242,7 @@ CG_STATE_WORDS, CG_DONE, CG_ITERATIONS = 8, 3, 4
 SIZE_QUERIES = {
     "sei_blur_sep_circ_lds": [_I, _I, _I, _I],
     "sei_blur_dense_pad_work_floats": [_I, _I, _I, _I, _I, _I, _I],
+    "sei_blur_decimate_work_floats": [_I, _I, _I, _I, _I, _I, _I, _I],
     "sei_resample_sepband_lds": [_I, _I, _I, _I, _I, _I, _I, _I],
     "sei_proposed_draws_max_numel": [],
     "sei_ssim_luma_work_floats": [_I, _I, _I],

@@ -17,6 +17,7 @@
 // pass has consumed it (see circ_filter_sep_kernel).
 #include "sei_common.h"
 #include "bicubic_taps.h"
+#include "blur_pad.h"
 
 #include <atomic>
 
@@ -122,24 +123,7 @@ __global__ __launch_bounds__(BLUR_THREADS) void blur_dense_circ_kernel(
 // extended by the padding on every side). Each tap row is summed on its own and the rows are then added in order: a
 // fixed order, and the rounding error of kh + kv additions instead of kv * kh.
 // ------------------------------------------------------------------------------------------------
-enum { PAD_REPLICATE = 1, PAD_REFLECT = 2, PAD_VALID = 3, PAD_ZERO = 4 };
-
-template <int MODE>
-__device__ __forceinline__ float pad_fetch(const float *__restrict__ xp, int e, int f, int H, int W) {
-    if (MODE == PAD_ZERO) return (e >= 0 && e < H && f >= 0 && f < W) ? xp[(size_t)e * W + f] : 0.f;
-    if (MODE == PAD_REFLECT) {
-        e = e < 0 ? -e : e;
-        e = e > H - 1 ? 2 * (H - 1) - e : e;
-        f = f < 0 ? -f : f;
-        f = f > W - 1 ? 2 * (W - 1) - f : f;
-    }
-    // the replicate rule. For the other two it only keeps the halo of a partial last tile inside the plane: their own
-    // rule leaves every position that feeds a written output in range already.
-    e = min(max(e, 0), H - 1);
-    f = min(max(f, 0), W - 1);
-    return xp[(size_t)e * W + f];
-}
-
+// (the staging maps, pad_fetch, are in blur_pad.h: blur_decimate.hip stages through them too)
 template <int MODE>
 __global__ __launch_bounds__(BLUR_THREADS) void blur_dense_pad_kernel(
     const float *__restrict__ x, float *__restrict__ y, const float *__restrict__ k, int kv, int kh,
@@ -586,11 +570,6 @@ struct BlurPadPlan {
     bool fold;
     size_t work;             // floats of Z (0: the tiled kernel writes y)
 };
-static void blur_pad_axis(int K, int &s, int &p) {
-    if (K == 1) s = 0, p = 1;
-    else if (K & 1) s = p = K / 2;
-    else s = K / 2 - 1, p = K / 2;
-}
 static int blur_pad_plan(int planes, int H, int W, int kv, int kh, int mode, int transpose, BlurPadPlan &pl) {
     SEI_REQUIRE(planes > 0 && H > 0 && W > 0 && kv > 0 && kh > 0);
     SEI_REQUIRE(mode == PAD_REPLICATE || mode == PAD_REFLECT || mode == PAD_VALID);
@@ -621,11 +600,6 @@ static int blur_pad_plan(int planes, int H, int W, int kv, int kh, int mode, int
     if ((size_t)planes * tiles >= ((size_t)1 << 31) || sei_ceil_div((size_t)planes * H * W, 256) >= ((size_t)1 << 31))
         return SEI_ERR_TOO_LARGE;
     return 0;
-}
-
-static bool floats_overlap(const float *a, size_t na, const float *b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
 }
 
 template <int MODE>
@@ -670,14 +644,18 @@ extern "C" int sei_blur_dense_pad(const float *x, float *y, const float *k, int 
     if (pl.fold) {
         const int status = sei_launch_status();
         if (status != 0) return status;
-        const unsigned grid = (unsigned)sei_ceil_div(full, 256);
-        if (mode == PAD_REPLICATE)
-            hipLaunchKernelGGL(blur_pad_fold_kernel<PAD_REPLICATE>, dim3(grid), dim3(256), 0, s, work, y, H, W, pl.pv, pl.ph,
-                               full);
-        else
-            hipLaunchKernelGGL(blur_pad_fold_kernel<PAD_REFLECT>, dim3(grid), dim3(256), 0, s, work, y, H, W, pl.pv, pl.ph,
-                               full);
+        return sei_blur_pad_fold_launch(mode, work, y, planes, H, W, pl.pv, pl.ph, s);
     }
+    return sei_launch_status();
+}
+
+int sei_blur_pad_fold_launch(int mode, const float *Z, float *out, int planes, int H, int W, int pv, int ph, hipStream_t s) {
+    const size_t full = (size_t)planes * H * W;
+    const unsigned grid = (unsigned)sei_ceil_div(full, 256);
+    if (mode == PAD_REPLICATE)
+        hipLaunchKernelGGL(blur_pad_fold_kernel<PAD_REPLICATE>, dim3(grid), dim3(256), 0, s, Z, out, H, W, pv, ph, full);
+    else
+        hipLaunchKernelGGL(blur_pad_fold_kernel<PAD_REFLECT>, dim3(grid), dim3(256), 0, s, Z, out, H, W, pv, ph, full);
     return sei_launch_status();
 }
 

@@ -143,6 +143,21 @@ def blur_axis_matrix(n, taps, mode):
     return m
 
 
+def blur_decimate_axis_matrix(n, taps, mode, rate, phase=0):
+    """Dense float64 (n_out, n) matrix of one axis of BlurDownsampling: the rows phase, phase + rate, ... of
+    blur_axis_matrix(n, taps, mode), n_out = ceil((n - phase) / rate) -- y[i'] = sum_a taps[a] x[map(rate i' + phase - a + s)].
+    `valid` is refused: the image is then not rate times the measurement."""
+    if mode == "valid":
+        raise ValueError("blur then decimate: padding='valid' is not part of this operator (the image is then not rate "
+                         "times the measurement); use circular, replicate or reflect")
+    rate, phase = int(rate), int(phase)
+    if rate < 1 or not 0 <= phase < rate:
+        raise ValueError(f"blur then decimate: needs a rate >= 1 and a phase in [0, rate), got rate {rate}, phase {phase}")
+    if phase >= n:
+        raise ValueError(f"blur then decimate: phase {phase} leaves no sample of an extent of {n}")
+    return np.ascontiguousarray(blur_axis_matrix(n, taps, mode)[phase::rate])
+
+
 def to_band(dense):
     """Dense (n_out, n_in) -> (weights (n_out, nb) f32, lo (n_out,) i32, nb, max step of lo).
     Band starts are made non-decreasing (a row whose leading weights are exact zeros of the cubic

@@ -146,6 +146,88 @@ class PaddedBlurOp:
         return y
 
 
+class BlurDecimateOp:
+    """y = (k (*) x)[..., phase::rate, phase::rate]: the blur of CircularBlurOp (mode 'circular') or PaddedBlurOp ('replicate',
+    'reflect') sampled every rate-th pixel, evaluating the kept samples only (the axis rule is
+    physics/_bands.blur_decimate_axis_matrix). Rank-1 kernels under replicate / reflect run as two banded axis matrices of
+    step `rate` through SeparableResampleOp, which transposes exactly; everything circular and every other kernel runs
+    sei_blur_decimate (`route` says which: 'bands' or 'kernel'). Taps, bands and the adjoint's workspace are made on the first
+    eager call per device and extent; later calls -- a capture among them -- hold launches only. Transposing without `out_hw`
+    assumes image extents (rate h, rate w)."""
+
+    MODES = {"circular": 0, "replicate": 1, "reflect": 2}
+
+    def __init__(self, kernel2d, rate, mode, phase=0):
+        if mode == "valid":
+            raise ValueError("BlurDecimateOp: padding='valid' is not part of this operator (the image is then not rate times "
+                             "the measurement); use one of " + ", ".join(self.MODES))
+        if mode not in self.MODES:
+            raise ValueError(f"BlurDecimateOp: padding must be one of {tuple(self.MODES)}, got {mode!r}")
+        rate, phase = int(rate), int(phase)
+        if not 1 <= rate <= 8:
+            raise ValueError(f"BlurDecimateOp: the rate must be in 1..8, got {rate}")
+        if not 0 <= phase < rate:
+            raise ValueError(f"BlurDecimateOp: the phase must be in [0, rate), got {phase} at rate {rate}")
+        k = kernel2d.detach().to("cpu", torch.float64).reshape(kernel2d.shape[-2], kernel2d.shape[-1]).numpy()
+        self.mode, self.rate, self.phase, self.shape = mode, rate, phase, k.shape
+        self.pad = (0, 0) if mode == "circular" else tuple(_bands.blur_axis_offsets(K)[1] for K in k.shape)
+        total = k.sum()
+        tv, th = k.sum(1), k.sum(0)
+        sep = np.outer(tv, th) / total if total != 0 else None
+        self.separable = sep is not None and np.abs(sep - k).max() <= 1e-12 * np.abs(k).max()
+        self.route = "bands" if self.separable and mode != "circular" else "kernel"
+        if self.route == "bands":
+            tv = tv / total
+            self._sep = SeparableResampleOp(lambda n: _bands.blur_decimate_axis_matrix(n, tv, mode, rate, phase),
+                                            inverse_length=lambda n: n * rate,
+                                            matrix_fn_w=lambda n: _bands.blur_decimate_axis_matrix(n, th, mode, rate, phase),
+                                            inverse_length_w=lambda n: n * rate)
+        else:
+            self._host = k
+        self._dev = {}         # device -> taps
+        self._work = {}        # (device, planes, H, W) -> the adjoint's Z canvas (as PaddedBlurOp: never evicted)
+
+    def out_length(self, n):
+        return (n - self.phase + self.rate - 1) // self.rate
+
+    def check_extent(self, H, W):
+        """The image extents this operator takes, refused by name before anything is built or launched."""
+        for n, K, p in zip((H, W), self.shape, self.pad):
+            if self.mode == "reflect" and p > n - 1:
+                raise ValueError(f"BlurDownsampling: padding='reflect' pads by {p} for a kernel of {K} taps, which an extent "
+                                 f"of {n} cannot mirror (image {H}x{W}, kernel {self.shape[0]}x{self.shape[1]})")
+            if self.phase >= n:
+                raise ValueError(f"BlurDownsampling: phase {self.phase} leaves no sample of an extent of {n} (image {H}x{W})")
+
+    def run(self, x, transpose, out_hw=None):
+        planes, h, w = _as_planes(x)
+        s = self.rate
+        H, W = (tuple(out_hw) if out_hw is not None else (s * h, s * w)) if transpose else (h, w)
+        self.check_extent(H, W)
+        ho, wo = self.out_length(H), self.out_length(W)
+        if transpose and (ho, wo) != (h, w):
+            raise ValueError(f"BlurDownsampling: the adjoint of a {H}x{W} image at rate {s}, phase {self.phase} takes "
+                             f"{ho}x{wo}, got {h}x{w}")
+        if self.route == "bands":
+            return self._sep.run(x, transpose, (H, W))
+        if x.device not in self._dev:
+            self._dev[x.device] = torch.tensor(self._host, dtype=torch.float32, device=x.device).contiguous()
+        k = self._dev[x.device]
+        kv, kh = self.shape
+        mode = self.MODES[self.mode]
+        y = torch.empty(x.shape[:-2] + ((H, W) if transpose else (ho, wo)), dtype=x.dtype, device=x.device)
+        work = None
+        floats = N.lib().sei_blur_decimate_work_floats(planes, H, W, kv, kh, mode, s, int(transpose))
+        if floats:
+            key = (x.device, planes, H, W)
+            if key not in self._work:
+                self._work[key] = torch.empty(floats, dtype=torch.float32, device=x.device)
+            work = self._work[key]
+        N.call("sei_blur_decimate", x.data_ptr(), y.data_ptr(), k.data_ptr(), kv, kh, planes, H, W, mode, s, self.phase,
+               self.phase, int(transpose), N.ptr(work))
+        return y
+
+
 # (n, None | inverse, eps, device) -> float32 first column; shared by every CirculantFilterOp. Never evicted: n floats
 # per distinct image extent, and a run sees a handful of extents.
 _CIRCULANT_COLUMNS = {}

@@ -43,3 +43,8 @@ class DefaultArgParser(ArgumentParser):
         # the boundary of the deblurring operator; anything but circular selects the legacy Blur ('valid' stays a
         # constructor argument: the losses and test.py need A(x) at the image's size)
         flag("--blur_padding", type=str, default="circular", choices=("circular", "replicate", "reflect"))
+        # the classical super-resolution degradation, (k * x)[P::sr_factor, P::sr_factor] (physics.BlurDownsampling): a kernel
+        # of the table or a torch.save'd 2-D tensor, as --kernel; None keeps the reference's antialiased bicubic Downsampling.
+        # --blur_padding picks its boundary, --physics_v2 its circular rule; --task sr only
+        flag("--sr_kernel", type=str, default=None)
+        flag("--sr_phase", type=int, default=0)
